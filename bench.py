@@ -2,7 +2,7 @@
 """
 bench.py -- utterances/s of the log-mel + x-vector train step on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -99,6 +99,12 @@ def parse_args():
                     help="after the timed region: replay the same captured steps for at least this long and report the rate as "
                          "`sustained` (0 disables).  The timed region of the driver's --steps 20 is ~45 ms; this block is long enough "
                          "for a 5-second utilisation sampler to see the GPU busy and for clocks to settle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32: "
+                         "loss, the updated parameters (params), their gradients (grads) and, when the model has any, the "
+                         "BatchNormalization moving statistics (state).  At most 64 MB in all; larger arrays are replaced by a "
+                         "fixed seeded sample of their elements.  Inputs are seeded, so runs with the same arguments compare "
+                         "output for output (bench_outputs/ is git-ignored for this)")
     ap.add_argument("--compute-dtype", choices=["float32", "bfloat16"], default=None,
                     help="GEMM arithmetic; float32 is the BASELINE metric's configuration, bfloat16 = config 5's "
                          "bf16-compute / fp32-master variant of the same workload (default: what the configuration names)")
@@ -414,6 +420,39 @@ def cpu_baseline(seconds, batch=PER_GPU_BATCH, config="xvector", num_langs=NUM_L
                 sample="%d train steps of %d utterances (%s, fp32, torch-CPU "
                        "restatement oracle/torch_ref.py; TensorFlow unavailable) in %.1f s on %d of %d logical "
                        "cores (best of a 8/16/32/64-thread sweep)" % (n, batch, what, dt, best_threads, ncpu))
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """write {name: array} as dirname/<name>.npy in float32, at most max_bytes in all.  The budget is shared out smallest
+    array first (each gets an equal part of what is left, so small arrays stay whole); an array larger than its part is cut
+    down to the elements at sorted indices drawn without replacement by a generator seeded with `seed` -- a function of the
+    array sizes only, so two runs of the same configuration sample the same elements.  Returns {name: shape written}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    keep, left = {}, max_bytes // 4
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].size, k))):
+        keep[name] = min(arrays[name].size, left // (len(arrays) - i))
+        left -= keep[name]
+    written = {}
+    for name, a in arrays.items():
+        if keep[name] < a.size:
+            idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(a.size, size=keep[name], replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def step_outputs(model, loss):
+    """host copies of what one train step leaves to its caller: the loss, the updated fp32 parameters, the gradient the
+    update used and the non-trainable state (BatchNormalization moving statistics) when the model has one"""
+    out = {"loss": np.array([loss], dtype=np.float32), "params": model.flat.cpu().numpy(), "grads": model.flat_grad.cpu().numpy()}
+    if getattr(model, "state_layout", None):
+        out["state"] = model.state.cpu().numpy()
+    return out
 
 
 def scaling_run_problem(gpus, nranks, backend, sync_active, grad_sync_mode, no_graph):
@@ -774,6 +813,9 @@ def main():
         torch.cuda.synchronize(dev)
 
     elapsed_local, first_loss, final_loss = timed_steps(trainer, batches, args.warmup, args.steps, sync_all, prefetch=args.prefetch)
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before any further step moves the weights
+        dumped = dump_outputs(args.dump_outputs, step_outputs(w["model"], final_loss))
     elapsed = elapsed_local
     rank_ms = None
     if world > 1:
@@ -856,6 +898,8 @@ def main():
     }
     if sustained is not None:
         result["sustained"] = sustained
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if rank_ms is not None:
         result["rank_ms_per_step"] = rank_ms
     if sync_active:

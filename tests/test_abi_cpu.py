@@ -368,6 +368,31 @@ def test_bench_refuses_a_scaling_run_that_is_not_what_it_claims():
         assert msg and "--gpus 8" in msg and "expected 8 ranks" in msg
 
 
+def test_bench_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (host logic): float32 .npy files, whole arrays under the budget, and over it a seeded sample
+    that is the same from call to call, so that two runs of the same configuration compare element for element"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    arrays = {"loss": np.array([0.5]), "params": rng.standard_normal((100, 30)), "grads": rng.standard_normal(3000)}
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert shapes == {"loss": [1], "params": [100, 30], "grads": [3000]}
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / "whole" / (k + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    budget = 2400                                                   # bytes: a tenth of the 6001 float32 elements ...
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays, max_bytes=budget)
+    b = bench.dump_outputs(str(tmp_path / "b"), arrays, max_bytes=budget)
+    assert a == b and sum(int(np.prod(s)) for s in a.values()) * 4 <= budget
+    for k in arrays:
+        x, y = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        assert np.isin(x, arrays[k].astype(np.float32)).all()        # ... drawn from the array itself
+    assert a == {"loss": [1], "params": [300], "grads": [299]}      # the loss whole, the rest split evenly
+
+
 def test_bucket_plan_is_contiguous_partition():
     """plan_buckets needs no device: use a layout-only stand-in with the x-vector's shapes"""
     from lidbox_amd.train import plan_buckets
