@@ -370,7 +370,7 @@ int lidbox_gemm_bf16s_last_carried(void);
  * (xvector.py:40, kernel 3 / stride 2: tf.keras computes it as one conv_backprop_input); here it is one GEMM per row residue of the
  * output-stationary form -- 492 tiles 1 024 deep and 396 tiles 512 deep at 512 utterances: 1.92 + 1.55 rounds of 256 CUs as two
  * launches, 3.47 as one grid.  Both problems must be launches lidbox_gemm_bf16s_nt would run on the 256 x 256 ping-pong tile without a
- * K split (gemm16_pp.h); anything else, or LIDBOX_GEMM16S_NO_PAIR=1, runs the two calls one after the other (the jobs ride with the
+ * K split (gemm16_pp.h); anything else runs the two calls one after the other (the jobs ride with the
  * first): same bits either way.  The outputs must not overlap; the operands may.  lidbox_gemm_bf16s_last_pair(): 1 if the calling
  * thread's most recent call ran as one grid. */
 int lidbox_gemm_bf16s_nt_pair_carry(lidbox_rows_t A16_0, const void* B16_0, long ldb0, lidbox_rows_out_t C0, void* C16_0, int K0, int N0,

@@ -368,18 +368,7 @@ extern "C" int lidbox_feat_plan_channels(const lidbox_feat_plan* p, int kind) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-#ifndef LBX_FEAT_NO_HOIST
-#define LBX_FEAT_NO_HOIST 1                  // keep the untangle's per-lane addresses out of loop-invariant registers
-#endif
-#ifndef LBX_FEAT_SEGMEL
-#define LBX_FEAT_SEGMEL 1                   // 0: always use the per-band CSR mel loop (A/B aid)
-#endif
-#ifndef LBX_FEAT_FAST_INTERIOR
-#define LBX_FEAT_FAST_INTERIOR 1            // 0: always take the guarded sample-load path (A/B aid)
-#endif
-#ifndef LBX_FEAT_WAVES
-#define LBX_FEAT_WAVES 3                    // waves per SIMD the register allocator aims for
-#endif
+constexpr int FEAT_WAVES = 3;              // waves per SIMD the register allocator aims for
 constexpr float LOG_EPS = 1e-6f;           // tf_utils.py:178
 constexpr int EXCH_ROW = 144;              // bytes: 8 x (2 complex) + 16 pad  -> conflict-free b128
 constexpr int EXCH_FRAME = 8 * EXCH_ROW;   // 1152 B per frame per half pass
@@ -415,43 +404,7 @@ struct FusedArgs {
     int iters;                  // tiles per wave
     int tiles_per_wg;           // consecutive tiles one workgroup owns (its waves take them round-robin)
     unsigned nwg;
-#if defined(LBX_FEAT_TIMING) || defined(LBX_FEAT_TIMELINE)
-    long long* stamps;          // [nwg*NW][16] s_memtime samples of each wave's LBX_FEAT_TIMING-th tile, 12 = kernel entry, 13 = tables staged,
-                                // 14 = wave exit, 15 = s_memrealtime at exit (debug builds only)
-#endif
 };
-
-// Debug builds.  -DLBX_FEAT_TIMING=k: per-phase s_memtime stamps of every wave's k-th tile (scheduling fences around each stamp:
-// the phase split is approximate and the build is slower).  -DLBX_FEAT_TIMELINE=k: only the kernel-level stamps and the k-th
-// tile's first and last, no fences (tools/feat_timeline.py).
-#ifdef LBX_FEAT_TIMELINE
-#define LBX_FEAT_TIMING LBX_FEAT_TIMELINE
-#define LBX_STAMP_FENCE() do { } while (0)
-#define LBX_STAMP_ON(i) ((i) == 0 || (i) == 8)
-#else
-#define LBX_STAMP_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LBX_STAMP_ON(i) true
-#endif
-#ifdef LBX_FEAT_TIMING
-#define LBX_STAMP(i)                                                                              \
-    do {                                                                                          \
-        LBX_STAMP_FENCE();                                                                        \
-        if (LBX_STAMP_ON(i) && it == LBX_FEAT_TIMING && lane == 0 && a.stamps)                    \
-            a.stamps[((long)blockIdx.x * NW + wave) * 16 + (i)] = (long long)__builtin_amdgcn_s_memtime(); \
-        LBX_STAMP_FENCE();                                                                        \
-    } while (0)
-#define LBX_STAMP_K(i)                                                                            \
-    do {                                                                                          \
-        LBX_STAMP_FENCE();                                                                        \
-        if ((threadIdx.x & 63) == 0 && a.stamps)                                                  \
-            a.stamps[((long)blockIdx.x * NW + (threadIdx.x >> 6)) * 16 + (i)] =                   \
-                ((i) == 15 || (i) == 11) ? (long long)__builtin_amdgcn_s_memrealtime() : (long long)__builtin_amdgcn_s_memtime(); \
-        LBX_STAMP_FENCE();                                                                        \
-    } while (0)
-#else
-#define LBX_STAMP(i) do { } while (0)
-#define LBX_STAMP_K(i) do { } while (0)
-#endif
 
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
@@ -531,15 +484,14 @@ __device__ __forceinline__ float lane_down(const float v, const int d, const int
 // Steps 2-6 of a tile.  za / zb: the windowed packed samples of lane q (n2 = 2q / 2q + 1, n1 = 0..15) of frame slot f.  Leaves
 // |X[bin]|^power of the wave's 8 frames in its power buffer (wbuf: [8][P_STRIDE], or TRANSPOSED [PT_ROWS][8] with one skew row per
 // 8 bins, so that the mel lanes -- one per run of bins -- read their 32-byte rows from different banks).  The exchange uses the same
-// bytes.  stamp(i): phase stamps of the timing builds.
-template <bool POW2, bool TRANSPOSED, int NIN = 16, typename Stamp>
+// bytes.
+template <bool POW2, bool TRANSPOSED, int NIN = 16>
 __device__ __forceinline__ void fft512_power_tile(float2 (&za)[16], float2 (&zb)[16], char* wbuf, const int q, const int f,
-                                                  const float2* s_tw256, const float2* s_tw512, const float power_half, Stamp&& stamp) {
+                                                  const float2* s_tw256, const float2* s_tw512, const float power_half) {
     float* s_P = reinterpret_cast<float*>(wbuf);
     // ---- 2. pass 1: DFT16 over n1 for both n2 -> A[n2][k1] in reg R16(k1)
     dft16<NIN>(za);
     dft16<NIN>(zb);
-    stamp(2);
     // ---- 3. twiddle by W256^(n2*k1)
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) {
@@ -547,17 +499,11 @@ __device__ __forceinline__ void fft512_power_tile(float2 (&za)[16], float2 (&zb)
         za[R16(k1)] = cmul(za[R16(k1)], make_float2(w.x, w.y));
         zb[R16(k1)] = cmul(zb[R16(k1)], make_float2(w.z, w.w));
     }
-    stamp(3);
     // ---- 4. exchange through LDS in two half passes; lane q ends with
     //         ua = A[0..15][k1 = q], ub = A[0..15][k1 = (16 - q) % 16, or 8 for q = 0]
     float2 ua[16], ub[16];
     char* ex = wbuf + f * EXCH_FRAME;
     wave_lds_sync();                                 // previous tile's readers are done
-#ifdef LBX_ABL_NOEXCH
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { ua[j] = za[j]; ub[j] = zb[j]; }
-    (void)ex;
-#else
 #pragma unroll
     for (int k1 = 0; k1 < 8; ++k1)
         *reinterpret_cast<float4*>(ex + k1 * EXCH_ROW + q * 16) =
@@ -582,13 +528,10 @@ __device__ __forceinline__ void fft512_power_tile(float2 (&za)[16], float2 (&zb)
         ub[2 * j] = make_float2(v.x, v.y);
         ub[2 * j + 1] = make_float2(v.z, v.w);
     }
-#endif
-    stamp(4);
     // ---- 5. pass 2: DFT16 over n2 -> Z'[k1 + 16*k2] in reg R16(k2)
     dft16(ua);
     dft16(ub);
     wave_lds_sync();                                 // exchange reads done before P overwrites
-    stamp(5);
     // ---- 6. untangle conjugate pairs, |.|^2, into the per-frame power buffer.
     //   q != 0 : slot s pairs ua[k2=s] (bin q+16s) with ub[k2=15-s] (bin 256-q-16s)
     // The per-lane bins / LDS addresses of this section depend only on q, so the compiler hoists them out of
@@ -596,9 +539,7 @@ __device__ __forceinline__ void fft512_power_tile(float2 (&za)[16], float2 (&zb)
     // reloads them here every tile (15 dependent scratch loads in the busiest phase of the kernel).  An opaque
     // copy of q keeps their (cheap) computation inside the loop instead.
     int qv = q;
-#if LBX_FEAT_NO_HOIST
     asm volatile("" : "+v"(qv));
-#endif
     // Power-buffer addresses: within slots 0-7 and within slots 8-15 the two bins of a slot move by +-16 per slot, and so do their rows
     // of the transposed layout (bin + bin / 8 moves by 18: 16 s is a multiple of 8), so four per-lane bases and immediate offsets
     // replace the per-store address arithmetic (round 4's census: 140 integer instructions per tile).
@@ -676,11 +617,8 @@ __device__ __forceinline__ void segmel_tile(const int lane, const int seg_len, c
     // lanes that cover the 64 banks once only when they hit 16 different 16-byte slots mod 256 bytes: with every lane on the FIRST half
     // of its row a group can reach 8 of the 16 slots (2-way conflicts by construction).  Odd lanes therefore read the second half first
     // -- each group holds 8 even and 8 odd lanes -- and carry frames 4-7 in acc[0..3], 0-3 in acc[4..7] until the swap below.  (Round 5
-    // measured this neutral on a kernel that was not LDS-bound, profiles/r05_feature_mel_halfswap_ab.txt; LBX_FEAT_MEL_HALFSWAP=0: off.)
-#ifndef LBX_FEAT_MEL_HALFSWAP
-#define LBX_FEAT_MEL_HALFSWAP 1
-#endif
-    const int half0 = (LBX_FEAT_MEL_HALFSWAP && (lane & 1)) ? 4 : 0, half1 = 4 - half0;
+    // measured this neutral on a kernel that was not LDS-bound, profiles/r05_feature_mel_halfswap_ab.txt.)
+    const int half0 = (lane & 1) ? 4 : 0, half1 = 4 - half0;
     for (int j0 = 0; j0 < seg_len; j0 += 4) {
         float w[4];
         float4 p0[4], p1[4];
@@ -701,14 +639,12 @@ __device__ __forceinline__ void segmel_tile(const int lane, const int seg_len, c
             acc[6] = fmaf(p1[u].z, w[u], acc[6]); acc[7] = fmaf(p1[u].w, w[u], acc[7]);
         }
     }
-    if (LBX_FEAT_MEL_HALFSWAP) {
-        const bool sw = (lane & 1) != 0;
+    const bool sw = (lane & 1) != 0;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float lo = acc[i], hi = acc[4 + i];
-            acc[i] = sw ? hi : lo;
-            acc[4 + i] = sw ? lo : hi;
-        }
+    for (int i = 0; i < 4; ++i) {
+        const float lo = acc[i], hi = acc[4 + i];
+        acc[i] = sw ? hi : lo;
+        acc[4 + i] = sw ? lo : hi;
     }
     const int sidx = sinfo & 255, sns = sinfo >> 8;
     for (int st = 0; st < seg_steps; ++st) {
@@ -821,7 +757,7 @@ __device__ __forceinline__ float store_mel_tile(const int lane, const int total,
 // not take: signals that are not 16-byte aligned (VEC4 = false), plans whose bands do not split into 64 runs (SEGMEL = false) or
 // whose tables leave the streaming shape fewer than 8 waves.
 template <int KIND, bool VEC4, bool POW2, bool SEGMEL>
-__global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(const FusedArgs a) {
+__global__ __launch_bounds__(256, FEAT_WAVES) void fused_feat512_kernel(const FusedArgs a) {
     constexpr int NW = 4, NT = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // ---- LDS carve: tables, then one scratch block per wave
@@ -846,8 +782,6 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
     const int wave_bytes = WAVE_SCRATCH + ((stage_floats * 4 + 15) & ~15);
 
     const int tid = threadIdx.x;
-    LBX_STAMP_K(11);
-    LBX_STAMP_K(12);
     for (int i = tid; i < 512; i += NT) s_win[i] = a.win512[i];
     if (tid < 256) {
         s_tw256[tid] = a.tw256[tid];
@@ -870,7 +804,6 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
                 for (int i = tid; i < a.M * a.ncoef; i += NT) s_dct[i] = a.dct[i];
     }
     __syncthreads();
-    LBX_STAMP_K(13);
 
     const int lane = tid & 63, wave = tid >> 6;
     const int q = lane & 7;          // lane within the frame
@@ -910,7 +843,6 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
         //         per load makes the compiler wait for each one before issuing the next: 13 serialized
         //         HBM round trips per tile): lanes whose samples lie outside the frame / utterance read
         //         four zeros instead.
-        LBX_STAMP(0);
         float2 za[16], zb[16];
         // Interior tiles (every read of the tile's 8 frames, up to sample 511 of the last one, stays inside the
         // utterance -- wave-uniform test; 24 of 25 tiles at 2 s): one base address per lane and immediate offsets,
@@ -918,7 +850,7 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
         // later samples and the window table is zero there.  The guarded path below handles an utterance's last tile.
         // (Round 2 also measured skipping the always-zero samples 416..511 of frames <= 416 samples behind a wave-uniform branch:
         // slower for log-mel, 28.7 vs 28.0 us at B = 256, neutral for MFCC; removed.)
-        const bool interior = VEC4 && LBX_FEAT_FAST_INTERIOR && (long)(t0 + 7) * a.S + 512 <= a.N;
+        const bool interior = VEC4 && (long)(t0 + 7) * a.S + 512 <= a.N;
         if (interior) {
             const float* base = src + 4 * q;
 #pragma unroll
@@ -965,10 +897,8 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        LBX_STAMP(1);
         // ---- 2.-6. FFT, untangling, |.|^power into the wave's power buffer
-        fft512_power_tile<POW2, SEGMEL>(za, zb, wbuf, q, f, s_tw256, s_tw512, a.power_half, [&](int i) { LBX_STAMP(i); });
-        LBX_STAMP(6);
+        fft512_power_tile<POW2, SEGMEL>(za, zb, wbuf, q, f, s_tw256, s_tw512, a.power_half);
 
         float* Pf = s_P + f * P_STRIDE;
         const int nvalid = min(8, a.T - t0);             // frames of this tile inside the utterance
@@ -1000,7 +930,6 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
                 }
             }
             wave_lds_sync();
-            LBX_STAMP(7);
             if (KIND == LIDBOX_FEAT_MFCC) {
                 float* s_coef = SEGMEL ? s_P : s_stage + 8 * a.M;
                 if (SEGMEL) {
@@ -1026,18 +955,15 @@ __global__ __launch_bounds__(256, LBX_FEAT_WAVES) void fused_feat512_kernel(cons
                 bad = store_mel_tile<false>(lane, nvalid * a.M, dst, nullptr, s_stage, bad);
             }
         }
-        LBX_STAMP(8);
     }
     if (a.nonfinite && bad != bad) *a.nonfinite = 1;
-    LBX_STAMP_K(14);
-    LBX_STAMP_K(15);
 }
 
 // ------------------------------------------------------------------------------------------------
 // streaming kernel (round 6): the fused tile as a software pipeline
 // ------------------------------------------------------------------------------------------------
 // Same tile arithmetic as fused_feat512_kernel (bit-identical results), different schedule.  Round 6's per-wave timeline of that
-// kernel at 256 utterances (tools/feat_timeline.py, profiles/r06_feature_timeline.txt): tables staged 1.6 us after entry, the first
+// kernel at 256 utterances (profiles/r06_feature_timeline.txt): tables staged 1.6 us after entry, the first
 // tile's samples requested only then; first tile 9.7 us median / 16.4 us p90 (every wave of the machine waits for HBM, then all of
 // them hit the LDS exchange together), second tile 7.2 us; waves leave between 15.8 and 25.5 us because 25 tiles per CU on 14 waves
 // is 2 + 2 + ... + 1 with the two-tile waves piled on two of the four SIMDs.  Per tile the LDS pipe is busy ~830 cycles (the
@@ -1084,8 +1010,6 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
     const int tid = threadIdx.x;
     const int lane0 = tid & 63;
     const int wave = (int)wave_uniform((unsigned)tid >> 6);
-    LBX_STAMP_K(11);
-    LBX_STAMP_K(12);
 
     const unsigned chunk = xcd_chunk_id(blockIdx.x, a.nwg);
     const unsigned tile0 = chunk * (unsigned)a.tiles_per_wg;
@@ -1108,12 +1032,8 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
         const int voff = (int)(t0 * (unsigned)a.S * ESZ + lane_off);
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-#ifdef LBX_ABL_NOLOAD
-            x[j] = (xreg_t)(unsigned)(voff + j);
-#else
             if constexpr (SRC16) x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, voff + 64 * j, 0, 0);
             else x[j] = __builtin_amdgcn_raw_buffer_load_b128(r, voff + 128 * j, 0, 0);
-#endif
         }
     };
     // Table loads first (one value per thread and table where the workgroup is wide enough), THEN the first tile's samples: loads
@@ -1154,7 +1074,6 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
     }
     if (tid == 0) *s_next = NW;
     __syncthreads();
-    LBX_STAMP_K(13);
 
     char* wbuf = smem + table_bytes + wave * WAVE_SCRATCH;
     float* s_P = reinterpret_cast<float*>(wbuf);          // SPECTROGRAM: [8][P_STRIDE]; else transposed [PT_ROWS][8]; aliases the exchange
@@ -1183,7 +1102,6 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
         const int t0 = (int)((tile - b * tpu) * 8u);
 
         // ---- 1. window.  lane q holds n2 = 2q (za) and 2q+1 (zb), n1 = 0..15: packed sample n = 16 n1 + n2 <-> reals 32 n1 + 4q .. + 3
-        LBX_STAMP(0);
         float2 za[16], zb[16];
 #pragma unroll
         for (int n1 = 0; n1 < NL; ++n1) {
@@ -1198,13 +1116,10 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
             za[n1] = make_float2(v.x * w.x, v.y * w.y);
             zb[n1] = make_float2(v.z * w.z, v.w * w.w);
         }
-        LBX_STAMP(1);
         // ---- 2.-6. FFT, untangling, |.|^power into the wave's power buffer
-        fft512_power_tile<POW2, KIND != LIDBOX_FEAT_SPECTROGRAM, NL>(za, zb, wbuf, q, f, s_tw256, s_tw512, a.power_half,
-                                                                 [&](int i) { LBX_STAMP(i); });
+        fft512_power_tile<POW2, KIND != LIDBOX_FEAT_SPECTROGRAM, NL>(za, zb, wbuf, q, f, s_tw256, s_tw512, a.power_half);
         // ---- 1'. the next tile's samples, into registers that are dead from here to the top of the loop
         issue(nxt, lane);
-        LBX_STAMP(6);
 
         const int nvalid = min(8, a.T - t0);
         if (KIND == LIDBOX_FEAT_SPECTROGRAM) {
@@ -1221,11 +1136,8 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
                 }
             }
         } else {
-#ifndef LBX_ABL_NOMEL
             segmel_tile<KIND>(lane, a.seg_len, a.seg_steps, a.M, s_segmeta, s_segw, s_P, s_stage);
-#endif
             wave_lds_sync();
-            LBX_STAMP(7);
             if (KIND == LIDBOX_FEAT_MFCC) {
                 float wd[8];
 #pragma unroll
@@ -1245,12 +1157,9 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
             }
         }
         badmask |= __builtin_amdgcn_ballot_w64(bad != bad);
-        LBX_STAMP(8);
         cur = nxt;
     }
     if (a.nonfinite && badmask != 0 && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) *a.nonfinite = 1;
-    LBX_STAMP_K(14);
-    LBX_STAMP_K(15);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1540,8 +1449,7 @@ int launch_stream_nl(const FusedArgs& a, int nw, size_t lds, hipStream_t st) {
 // it, their window products and the zero inputs of pass 1's first radix-4 stage are compiled out (NL = 13)
 template <int KIND, bool POW2, bool SHADOW, bool SRC16>
 int launch_stream_one(const FusedArgs& a, int nw, size_t lds, hipStream_t st) {
-    static const bool no_prune = getenv("LIDBOX_FEAT_NO_PRUNE") != nullptr;      // A/B aid
-    if (a.L <= 416 && !no_prune) return launch_stream_nl<KIND, POW2, SHADOW, SRC16, 13>(a, nw, lds, st);
+    if (a.L <= 416) return launch_stream_nl<KIND, POW2, SHADOW, SRC16, 13>(a, nw, lds, st);
     return launch_stream_nl<KIND, POW2, SHADOW, SRC16, 16>(a, nw, lds, st);
 }
 
@@ -1638,33 +1546,27 @@ extern "C" int lidbox_extract_features_fwd_ex(const lidbox_feat_plan* p, int kin
         if (a.dct_runs > p->M) a.dct_runs = p->M;
         a.dct_len = (p->M + a.dct_runs - 1) / a.dct_runs;
         a.dct_runs = (p->M + a.dct_len - 1) / a.dct_len;          // drop runs that would be empty
-        static const bool no_segmel = getenv("LIDBOX_FEAT_NO_SEGMEL") != nullptr;      // A/B aid
-        const bool segmel = LBX_FEAT_SEGMEL && p->seg_ok && !no_segmel && kind != LIDBOX_FEAT_SPECTROGRAM;
+        const bool segmel = p->seg_ok && kind != LIDBOX_FEAT_SPECTROGRAM;
         a.win512 = src16 ? p->d_win512_pcm : p->d_win512; a.tw256 = p->d_tw256; a.tw512 = p->d_tw512;
         a.mel_start = p->d_mel_start; a.mel_cnt = p->d_mel_cnt; a.mel_off = p->d_mel_off;
         a.mel_w = p->d_mel_w; a.dct = p->d_dct; a.out = out; a.out_bs = out_batch_stride;
         a.out16 = nullptr;
         a.nonfinite = nonfinite;
-#if defined(LBX_FEAT_TIMING) || defined(LBX_FEAT_TIMELINE)
-        a.stamps = (workspace && workspace_bytes >= (size_t)4096 * 4 * 16 * 8) ? (long long*)workspace : nullptr;
-#endif
         a.tiles_per_utt = (T + 7) / 8;
         a.ntiles = (long)B * a.tiles_per_utt;
         // float4 (short4) loads need 16-byte (8-byte) aligned frames
         const bool vec4 = (((uintptr_t)signals & (src16 ? 7 : 15)) == 0) && (sig_stride % 4 == 0) && (p->S % 4 == 0) && (p->L % 4 == 0);
 
         // ---- streaming kernel: one persistent workgroup per CU, all the waves the LDS holds, every CU the same number of consecutive
-        //      tiles (+- 1) handed out dynamically.  LIDBOX_FEAT_STREAM=0 keeps the round-1 shape (A/B aid).
+        //      tiles (+- 1) handed out dynamically.
         {
-            static const int stream_env = getenv("LIDBOX_FEAT_STREAM") ? atoi(getenv("LIDBOX_FEAT_STREAM")) : 1;
             const int table_floats = 1536 + (kind == LIDBOX_FEAT_SPECTROGRAM ? 0 : mel_table_floats(true, p->M, p->nnz, p->seg_len)) +
                                      (kind == LIDBOX_FEAT_MFCC ? p->M * p->ncoef : 0);
             const int table_bytes = (table_floats * 4 + 4 + 15) & ~15;
             int nw = (160 * 1024 - table_bytes) / WAVE_SCRATCH;
             if (nw > 16) nw = 16;
-            if (const char* e = getenv("LIDBOX_FEAT_STREAM_NW")) { const int v = atoi(e); if (v >= 1 && v < nw) nw = v; }      // tuning aid
             const bool fits32 = (long)N * 4 < (1L << 31) && a.ntiles < (1L << 31) && (long)(T + 8) * p->S * 4 < (1L << 31);
-            if (stream_env != 0 && vec4 && fits32 && nw >= 8 && (segmel || kind == LIDBOX_FEAT_SPECTROGRAM) && (!src16 || p->power == 2.0f)) {
+            if (vec4 && fits32 && nw >= 8 && (segmel || kind == LIDBOX_FEAT_SPECTROGRAM) && (!src16 || p->power == 2.0f)) {
                 int ncu = 256;
                 (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device);
                 if (ncu < 1) ncu = 256;
@@ -1702,10 +1604,9 @@ extern "C" int lidbox_extract_features_fwd_ex(const lidbox_feat_plan* p, int kin
         // grid: about four dispatch rounds of resident workgroups, equal tile counts per wave.  One tile per wave
         // while that holds (B <= ~490 at 2 s): the dispatcher then balances the tail; measured 35 vs 39 us at B = 256
         // against three tiles per wave on two thirds of the slots, and no difference at B = 2048.
-        const long max_wg = 256 * LBX_FEAT_WAVES;
+        const long max_wg = 256 * FEAT_WAVES;
         const long wg_needed = lbx_cdiv(a.ntiles, 4);
         a.iters = (int)lbx_cdiv(wg_needed, 4 * max_wg);
-        if (const char* e = getenv("LIDBOX_FEAT_ITERS")) { const int v = atoi(e); if (v >= 1) a.iters = v; }   // tuning aid
         a.nwg = (unsigned)lbx_cdiv(a.ntiles, 4L * a.iters);
         a.tiles_per_wg = 4 * a.iters;
         int rc;

@@ -51,41 +51,14 @@
 
 namespace {
 
-#ifndef LBX_GEMM_BK
-#define LBX_GEMM_BK 16
-#endif
-#ifndef LBX_GEMM_PRIO
-#define LBX_GEMM_PRIO 3                    // s_setprio level of the MFMA phase (0 = leave the default)
-#endif
-constexpr int BK = LBX_GEMM_BK;           // K depth of one LDS tile (tuning aid: -DLBX_GEMM_BK=32)
-#ifndef LBX_GEMM_WAVES_HINT
-#define LBX_GEMM_WAVES_HINT 1              // occupancy hint per tile shape: the register allocator then keeps the batched
-                                           // epilogue (gemm_shared.h) inside the K loop's budget -- 64x64: 56 registers
-                                           // (8 waves/SIMD), 128x64: 73 (6), 128x128: 116 (4); without it 72 / 104 / 180
-#endif
-#ifndef LBX_GEMM_MASK_PREFETCH
-#define LBX_GEMM_MASK_PREFETCH 0           // 1: fetch the ReLU mask as bits inside the K loop (A/B: 2375 vs 2355 us -- the mask
-                                           // costs bandwidth / issue slots, not epilogue latency)
-#endif
-#ifndef LBX_GEMM_WAVES_128
-#define LBX_GEMM_WAVES_128 3               // waves/SIMD asked for 128x128 tiles (4 would need <= 128 registers)
-#endif
-#ifndef LBX_GEMM_TN_HINT
-#define LBX_GEMM_TN_HINT 1                 // 1: hint on the 128x128 wgrad kernel only (-2.5 % on the three launches that use it;
-                                           // 2: on every wgrad tile -- 64x64 and 128x64 measured 8-27 % SLOWER with it)
-#endif
-#if LBX_GEMM_WAVES_HINT
-#define LBX_ROWS_BOUNDS(BM, BN) __launch_bounds__(256, ((BM) * (BN) >= 16384 ? LBX_GEMM_WAVES_128 : ((BM) * (BN) >= 8192 ? 6 : 8)))
-#else
-#define LBX_ROWS_BOUNDS(BM, BN) __launch_bounds__(256)
-#endif
-#if LBX_GEMM_TN_HINT == 2
-#define LBX_TN_BOUNDS(BM, BN) LBX_ROWS_BOUNDS(BM, BN)
-#elif LBX_GEMM_TN_HINT == 1
-#define LBX_TN_BOUNDS(BM, BN) __launch_bounds__(256, ((BM) * (BN) >= 16384 ? LBX_GEMM_WAVES_128 : 1))
-#else
-#define LBX_TN_BOUNDS(BM, BN) __launch_bounds__(256)
-#endif
+constexpr int BK = 16;                    // K depth of one LDS tile
+// Occupancy hint per tile shape: the register allocator then keeps the batched epilogue (gemm_shared.h) inside the K loop's
+// budget -- 64x64: 56 registers (8 waves/SIMD), 128x64: 73 (6), 128x128: 116 (4); without it 72 / 104 / 180.  128x128 tiles
+// ask for 3 waves/SIMD (4 would need <= 128 registers).
+#define LBX_ROWS_BOUNDS(BM, BN) __launch_bounds__(256, ((BM) * (BN) >= 16384 ? 3 : ((BM) * (BN) >= 8192 ? 6 : 8)))
+// wgrad: the hint on the 128x128 kernel only (-2.5 % on the three launches that use it; on every wgrad tile, 64x64 and
+// 128x64 measured 8-27 % SLOWER with it)
+#define LBX_TN_BOUNDS(BM, BN) __launch_bounds__(256, ((BM) * (BN) >= 16384 ? 3 : 1))
 
 // ---- K-inner operand (contraction index contiguous in HBM): ROWS x BK tile, transposed into
 //      LDS [BK][ROWS + 2].  Each thread keeps one source pointer per pass and bumps it by BK.
@@ -94,7 +67,7 @@ constexpr int BK = LBX_GEMM_BK;           // K depth of one LDS tile (tuning aid
 //      all; only the tail step (CHECK) tests k and zero-fills.
 template <int ROWS, bool ALIGNED, int NT = 256>
 struct KInnerLoader {
-    static constexpr int F4R = BK / 4;                // float4 per tile row: 4 (BK 16) or 8 (BK 32)
+    static constexpr int F4R = BK / 4;                // float4 per tile row: 4
     static constexpr int RPP = NT / F4R;              // tile rows per pass: 64 or 32 (256 threads), 128 (512)
     static constexpr int PASSES = ROWS >= RPP ? ROWS / RPP : 1;
     static constexpr bool PARTIAL = ROWS < RPP;       // more threads than float4s in the tile: the upper ones idle
@@ -231,7 +204,7 @@ __device__ __forceinline__ void mma_tile(const float* As, const float* Bs, int w
     float a[2][MI], b[2][NJ];
     // Waves in their MFMA phase outrank co-resident waves that are in the load/store/barrier phase
     // (measured in tools/micro/gemm_loop.hip: +5 % at 3 workgroups/CU, +15 % at 1).
-    if (LBX_GEMM_PRIO) __builtin_amdgcn_s_setprio(LBX_GEMM_PRIO);
+    __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int i = 0; i < MI; ++i) a[0][i] = ap[32 * i];
 #pragma unroll
@@ -252,17 +225,8 @@ __device__ __forceinline__ void mma_tile(const float* As, const float* Bs, int w
             for (int j = 0; j < NJ; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
     }
-    if (LBX_GEMM_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 }
-
-#ifdef LBX_GEMM_TIMING
-// Debug builds only (tools/gemm_phases.py): per-wave s_memtime samples of the rows kernels.
-//   [0] kernel entry  [1] first tile staged (after the first barrier)  [2] K loop done  [3] epilogue done
-//   [4] cycles inside mma_tile, [5] issuing the next tile's global loads, [6] LDS stores (incl. the wait for those loads),
-//   [7] waiting at the barrier -- summed over the K steps; [8] SIMD/CU/XCD id word (HW_ID)
-__device__ long long* g_gemm_stamps = nullptr;
-#define LBX_T() ((long long)__builtin_amdgcn_s_memtime())
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] . B)    B_KINNER = false: B[K][N] (NN)   true: B[N][K] (NT)
@@ -287,9 +251,6 @@ __device__ __forceinline__ void gemm_rows_body(const RowsD& A, const float* __re
     __shared__ __attribute__((aligned(16))) float Bs[2][BK * LDB];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef LBX_GEMM_TIMING
-    long long ts0 = LBX_T(), t_mma = 0, t_ld = 0, t_st = 0, t_bar = 0;
-#endif
     const int wm = wave / WN, wn = wave % WN;
     const unsigned chunk = xcd_chunk_id(blockIdx.x, ntiles);
     const int tn = chunk % tiles_n;
@@ -326,41 +287,15 @@ __device__ __forceinline__ void gemm_rows_body(const RowsD& A, const float* __re
         else lbo.store(Bs[0]);
     }
     __syncthreads();
-#ifdef LBX_GEMM_TIMING
-    const long long ts1 = LBX_T();
-#endif
 
-    // Backward epilogues multiply by the ReLU mask (aux > 0, aux = the forward activation, C's layout).  Reading
-    // it in the epilogue costs one dependent HBM round trip per output row while the workgroup holds its slot
-    // without issuing MFMAs (PMC: 31 % of wave cycles parked in the NT launches vs 18 % in NN).  Instead every
-    // lane fetches its 16*MI*NJ mask values two per K-step, ahead of that step's tile loads (so they are back
-    // when the tile is), and keeps them as bits: the epilogue is store-only.
-    constexpr int NPRE = 16 * MI * NJ;
-    const bool pre_mask = LBX_GEMM_MASK_PREFETCH && gridDim.y == 1 &&
-                          (epi == LIDBOX_EPI_RELU_MASK || epi == LIDBOX_EPI_ACCUM_RELU_MASK);
-    unsigned long long mbits = 0ull;
-    auto mask_ptr = [&](int idx) -> const float* {
-        const int r = idx & 15, blk = idx >> 4, bj = blk % NJ, bi = blk / NJ;
-        const long row = m0 + wm * (32 * MI) + bi * 32 + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2);
-        const int col = n0 + wn * (32 * NJ) + bj * 32 + (lane & 31);
-        return aux + ((row < M && col < N) ? row_offset(Cd, (unsigned)row) + col : 0);
-    };
+    // Backward epilogues read the ReLU mask in store_rows_tile.  Fetching it as bits inside the K loop instead was measured
+    // slower (2375 vs 2355 us): the mask costs bandwidth / issue slots, not epilogue latency.
 
     // The prefetch of step kt targets tile kt+1; only the LAST tile can be partial, so interior
     // prefetches carry no predicates (a wave-uniform scalar branch picks the variant).  One MMA
     // site keeps the accumulators in place.
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
-        const bool mload = pre_mask && 2 * kt < NPRE;        // wave-uniform
-        float mv0 = 0.f, mv1 = 0.f;
-        if (mload) {
-            mv0 = *mask_ptr(2 * kt);
-            mv1 = *mask_ptr(2 * kt + 1);
-        }
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q0 = LBX_T();
-#endif
         if (kt + 2 < nk) {
             la.template load<false>(kend);
             if (B_KINNER) lbi.template load<false>(kend);
@@ -370,50 +305,15 @@ __device__ __forceinline__ void gemm_rows_body(const RowsD& A, const float* __re
             if (B_KINNER) lbi.template load<true>(kend);
             else lbo.template load_plain<true>(kend);
         }
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q1 = LBX_T();
-#endif
         mma_tile<MI, NJ, LDA, LDB>(As[cur], Bs[cur], wm, wn, lane, acc);
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q2 = LBX_T();
-#endif
         if (kt + 1 < nk) {
             la.store(As[cur ^ 1]);
             if (B_KINNER) lbi.store(Bs[cur ^ 1]);
             else lbo.store(Bs[cur ^ 1]);
         }
-        if (mload)
-            mbits |= ((unsigned long long)(mv0 > 0.f) << (2 * kt)) | ((unsigned long long)(mv1 > 0.f) << (2 * kt + 1));
-#ifdef LBX_GEMM_TIMING
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q3 = LBX_T();
-#endif
         __syncthreads();
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q4 = LBX_T();
-        t_ld += q1 - q0; t_mma += q2 - q1; t_st += q3 - q2; t_bar += q4 - q3;
-#endif
     }
-#ifdef LBX_GEMM_TIMING
-    const long long ts2 = LBX_T();
-#endif
-    if (pre_mask)                                            // short K: the values no K-step fetched
-        for (int idx = 2 * nk; idx < NPRE; ++idx) mbits |= (unsigned long long)(*mask_ptr(idx) > 0.f) << idx;
-
-    store_rows_tile<MI, NJ>(acc, m0, n0, wm, wn, lane, m_beg, M, N, epi, aux, Cd, P, split, mbits, pre_mask);
-#ifdef LBX_GEMM_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0 && g_gemm_stamps) {
-        long long* o = g_gemm_stamps + ((long)(blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) + wave) * 10;
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = LBX_T(); o[4] = t_mma; o[5] = t_ld; o[6] = t_st; o[7] = t_bar; o[8] = hwid; o[9] = nk;
-    }
-#endif
+    store_rows_tile<MI, NJ>(acc, m0, n0, wm, wn, lane, m_beg, M, N, epi, aux, Cd, P, split);
 }
 
 template <int BM, int BN, bool B_KINNER, bool ALIGNED>
@@ -519,58 +419,27 @@ __global__ LBX_TN_BOUNDS(BM, BN) void gemm_tn_kernel(RowsD A, RowsD Bd, float* _
     const bool do_csum = (Pc != nullptr) && tk == 0 && tid < BN;
 
     const int nk = (int)((mend - mbeg + BK - 1) / BK);
-#ifdef LBX_GEMM_TIMING
-    long long ts0 = LBX_T(), t_mma = 0, t_ld = 0, t_st = 0, t_bar = 0;
-#endif
     if (nk > 0) {
         LBX_TN_FETCH(true)
         la.store(As[0]);
         lb.store(Bs[0]);
     }
     __syncthreads();
-#ifdef LBX_GEMM_TIMING
-    const long long ts1 = LBX_T();
-#endif
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q0 = LBX_T();
-#endif
         if (kt + 2 < nk) LBX_TN_FETCH(false)
         else if (kt + 1 < nk) LBX_TN_FETCH(true)
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q1 = LBX_T();
-#endif
         mma_tile<MI, NJ, LAo::LD, LBo::LD>(As[cur], Bs[cur], wm, wn, lane, acc);
         if (do_csum) {
 #pragma unroll
             for (int kk = 0; kk < BK; ++kk) csum += Bs[cur][kk * LBo::LD + tid];
         }
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q2 = LBX_T();
-#endif
         if (kt + 1 < nk) {
             la.store(As[cur ^ 1]);
             lb.store(Bs[cur ^ 1]);
         }
-#ifdef LBX_GEMM_TIMING
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q3 = LBX_T();
-#endif
         __syncthreads();
-#ifdef LBX_GEMM_TIMING
-        __builtin_amdgcn_sched_barrier(0);
-        const long long q4 = LBX_T();
-        t_ld += q1 - q0; t_mma += q2 - q1; t_st += q3 - q2; t_bar += q4 - q3;
-#endif
     }
-#ifdef LBX_GEMM_TIMING
-    const long long ts2 = LBX_T();
-#endif
 #undef LBX_TN_FETCH
     float* Pd = P + (long)split * K1 * N;
     const int h = lane >> 5, l = lane & 31;
@@ -587,13 +456,6 @@ __global__ LBX_TN_BOUNDS(BM, BN) void gemm_tn_kernel(RowsD A, RowsD Bd, float* _
             }
     }
     if (do_csum && n0 + tid < N) Pc[(long)split * N + n0 + tid] = csum;
-#ifdef LBX_GEMM_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0 && g_gemm_stamps) {
-        long long* o = g_gemm_stamps + ((long)blockIdx.x * 4 + wave) * 10;
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = LBX_T(); o[4] = t_mma; o[5] = t_ld; o[6] = t_st; o[7] = t_bar; o[8] = 0; o[9] = nk;
-    }
-#endif
 }
 
 // column sums (standalone): stage 1 partial[rs][N] over row slices, stage 2 fixed-order reduce
@@ -819,7 +681,7 @@ thread_local int g_last_carried = 0;      // whether the most recent lidbox_gemm
 const int CAND[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
 // steady state of the LDS-DMA kernels (gemm_dma.h; profiles/r03_dma_staircase.txt): 137 / 134 / 133 / 131 TFLOP/s
 const double TILE_EFF[4] = {1.0, 0.98, 0.97, 0.955};
-const int RESIDENT[4] = {BK == 16 ? 3 : 2, BK == 16 ? 4 : 3, BK == 16 ? 4 : 3, BK == 16 ? 6 : 4};   // workgroups per CU (VGPR / LDS limited)
+const int RESIDENT[4] = {3, 4, 4, 6};   // workgroups per CU (VGPR / LDS limited)
 const double FIXED_STEPS[4] = {6.0, 5.0, 5.0, 3.0};       // prologue + epilogue of one tile, in K-steps (fewer residents hide less of it)
 
 inline double conc_eff(double w) {
@@ -848,13 +710,12 @@ RowsChoice choose_rows(int kind, long M, int N, int K, size_t ws_bytes) {
     if (const TunedGemm* t = tuned_gemm(kind, M, N, K)) {
         const int kps = (int)(lbx_cdiv(lbx_cdiv(K, t->splits), BK) * BK);
         const int splits = (int)lbx_cdiv(K, kps);
-        if (!(BK > 16 && t->bm == 128 && t->bn == 128) &&
-            (splits == 1 || (size_t)splits * M * N * sizeof(float) <= ws_bytes))
-            return RowsChoice{t->bm, t->bn, splits, kps, t->no_tail_split != 0, (t->waves == 8 && t->bm == 128 && BK == 16) ? 8 : 4};
+        if (splits == 1 || (size_t)splits * M * N * sizeof(float) <= ws_bytes)
+            return RowsChoice{t->bm, t->bn, splits, kps, t->no_tail_split != 0, (t->waves == 8 && t->bm == 128) ? 8 : 4};
     }
     RowsChoice best{128, 128, 1, K};
     double best_cost = 1e30;
-    for (int c = (BK > 16 ? 1 : 0); c < 4; ++c) {
+    for (int c = 0; c < 4; ++c) {
         const int bm = CAND[c][0], bn = CAND[c][1];
         const long tiles = lbx_cdiv(M, bm) * lbx_cdiv(N, bn);
         for (int s = 1; s <= 64; s *= 2) {
@@ -871,7 +732,7 @@ RowsChoice choose_rows(int kind, long M, int N, int K, size_t ws_bytes) {
     return best;
 }
 
-// the decomposition a launch uses: the planner's, or the tuning overrides LIDBOX_GEMM_PLAN / LIDBOX_GEMM_TILE
+// the decomposition a launch uses: the planner's, or the tuning override LIDBOX_GEMM_PLAN
 RowsChoice choose_rows_env(int kind, long M, int N, int K, size_t wsb) {
     RowsChoice ch = choose_rows(kind, M, N, K, wsb);
     if (M >= 4096) {                  // A/B aids: conv-size dgrads (LIDBOX_GEMM_NT8) / forward GEMMs (LIDBOX_GEMM_NN8) on the eight-wave 128 x bn tiles
@@ -882,18 +743,11 @@ RowsChoice choose_rows_env(int kind, long M, int N, int K, size_t wsb) {
     }
     if (const char* f = getenv("LIDBOX_GEMM_PLAN")) {             // tuning aid (tools/gemm_sweep.py): "bm,bn,splits"
         int bm = 0, bn = 0, sp = 0, wv = 4;
-        if (sscanf(f, "%d,%d,%d,%d", &bm, &bn, &sp, &wv) >= 3 && (bm == 64 || bm == 128) && (bn == 64 || bn == 128) && sp >= 1 &&
-            !(BK > 16 && bm == 128 && bn == 128)) {
+        if (sscanf(f, "%d,%d,%d,%d", &bm, &bn, &sp, &wv) >= 3 && (bm == 64 || bm == 128) && (bn == 64 || bn == 128) && sp >= 1) {
             const int kps = (int)(lbx_cdiv(lbx_cdiv(K, sp), BK) * BK);
             const int splits = (int)lbx_cdiv(K, kps);
             if (splits == 1 || (size_t)splits * M * N * sizeof(float) <= wsb)
-                ch = RowsChoice{bm, bn, splits, kps, false, (wv == 8 && bm == 128 && BK == 16) ? 8 : 4};
-        }
-    } else if (const char* f = getenv("LIDBOX_GEMM_TILE")) {      // tuning aid: "128x128" etc.
-        int bm = 0, bn = 0;
-        if (sscanf(f, "%dx%d", &bm, &bn) == 2 && (bm == 64 || bm == 128) && (bn == 64 || bn == 128)) {
-            ch.bm = bm; ch.bn = bn; ch.splits = 1; ch.k_per_split = K; ch.no_tail_split = false;
-            if (BK > 16 && bm == 128 && bn == 128) ch.bn = 64;
+                ch = RowsChoice{bm, bn, splits, kps, false, (wv == 8 && bm == 128) ? 8 : 4};
         }
     }
     return ch;
@@ -1036,13 +890,10 @@ int launch_rows_range(const RowsChoice& ch, bool al, RowsD Ad, const float* Bm, 
         else if (ch.bn == 128) LBX_ROWS_DMA(64, 128);
         else LBX_ROWS_DMA(64, 64);
     } else
-#if LBX_GEMM_BK == 16
     if (ch.waves == 8 && ch.bm == 128 && ch.bn == 128) LBX_ROWS8(128, 128);
     else if (ch.waves == 8 && ch.bm == 128 && ch.bn == 64) LBX_ROWS8(128, 64);
     else if (ch.bm == 128 && ch.bn == 128) LBX_ROWS(128, 128);
-    else
-#endif
-    if (ch.bm == 128) LBX_ROWS(128, 64);
+    else if (ch.bm == 128) LBX_ROWS(128, 64);
     else if (ch.bn == 128) LBX_ROWS(64, 128);
     else LBX_ROWS(64, 64);
 #undef LBX_ROWS
@@ -1077,7 +928,7 @@ int launch_rows(lidbox_rows_t A, const float* Bm, long ldb, lidbox_rows_out_t Cd
     float* P = (float*)ws;
 
     // persistent stream-K kernel (gemm_sk.h): aligned problems that fill the chip, workspace permitting
-    if (al && !getenv("LIDBOX_GEMM_PLAN") && !getenv("LIDBOX_GEMM_TILE") && aligned16(ws) && !sk_tuned_out(B_KINNER ? 1 : 0, M, N, K) &&
+    if (al && !getenv("LIDBOX_GEMM_PLAN") && aligned16(ws) && !sk_tuned_out(B_KINNER ? 1 : 0, M, N, K) &&
         sk_b_extent_ok(B_KINNER, K, N, ldb)) {
         // the pipelined variant: its in-loop epilogue addresses C rows with at most one utterance wrap per 32-row block
         // (its drain stages the mask / old values of C through LDS-DMA: 16-byte aligned C rows, whole 16-byte column chunks)
@@ -1175,21 +1026,18 @@ TnPlan tn_plan(long M, int K1, int N) {
     if (const char* f = getenv("LIDBOX_GEMM_TN_PLAN")) {          // tuning aid (tools/gemm_sweep.py): "bm,bn,splits"
         int bm = 0, bn = 0;
         long sp = 0;
-        if (sscanf(f, "%d,%d,%ld", &bm, &bn, &sp) == 3 && (bm == 64 || bm == 128) && (bn == 64 || bn == 128) && sp >= 1 &&
-            !(BK > 16 && bm == 128 && bn == 128)) {
+        if (sscanf(f, "%d,%d,%ld", &bm, &bn, &sp) == 3 && (bm == 64 || bm == 128) && (bn == 64 || bn == 128) && sp >= 1) {
             const long rps = lbx_cdiv(lbx_cdiv(M, sp), BK) * BK;
             return TnPlan{bm, bn, (int)lbx_cdiv(M, rps), rps};
         }
     }
     if (const TunedGemm* t = tuned_gemm(2, M, N, K1)) {
-        if (!(BK > 16 && t->bm == 128 && t->bn == 128)) {
-            const long rps = lbx_cdiv(lbx_cdiv(M, (long)t->splits), BK) * BK;
-            return TnPlan{t->bm, t->bn, (int)lbx_cdiv(M, rps), rps};
-        }
+        const long rps = lbx_cdiv(lbx_cdiv(M, (long)t->splits), BK) * BK;
+        return TnPlan{t->bm, t->bn, (int)lbx_cdiv(M, rps), rps};
     }
     TnPlan best{128, 128, 1, M};
     double best_cost = 1e30;
-    for (int c = (BK > 16 ? 1 : 0); c < 4; ++c) {
+    for (int c = 0; c < 4; ++c) {
         const int bm = CAND[c][0], bn = CAND[c][1];
         const long tiles = lbx_cdiv(K1, bm) * lbx_cdiv(N, bn);
         for (long target = NUM_CU; target <= 8 * NUM_CU; target += NUM_CU / 2) {
@@ -1255,7 +1103,7 @@ extern "C" int lidbox_gemm_last_family(void) { return g_last_family; }
 
 extern "C" int lidbox_gemm_plan_stream_tail(int kind, long M, int N, int K, size_t workspace_bytes) {
     if (M <= 0 || N <= 0 || K <= 0 || kind < 0 || kind > 1 || dma_mode() == 0) return 0;
-    if (!getenv("LIDBOX_GEMM_PLAN") && !getenv("LIDBOX_GEMM_TILE") && lidbox_gemm_plan_is_stream_k(kind, M, N, K, workspace_bytes)) return 0;
+    if (!getenv("LIDBOX_GEMM_PLAN") && lidbox_gemm_plan_is_stream_k(kind, M, N, K, workspace_bytes)) return 0;
     const RowsChoice ch = choose_rows_env(kind, M, N, K, workspace_bytes);
     if (ch.splits != 1) return 0;
     const DmaStreamPlan spl = dma_stream_plan(ch.bm, ch.bn, M, N, K);
@@ -1299,12 +1147,6 @@ extern "C" int lidbox_gemm_nn(lidbox_rows_t A, const float* Bm, long ldb, lidbox
     return launch_rows<false>(A, Bm, ldb, C, K, N, epilogue, aux, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-#ifdef LBX_GEMM_TIMING
-extern "C" int lidbox_gemm_debug_set_stamps(void* device_ptr) {          // timing builds only (not in include/lidbox_hip.h)
-    LBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_stamps), &device_ptr, sizeof(void*)));
-    return LIDBOX_OK;
-}
-#endif
 
 extern "C" int lidbox_gemm_nt(lidbox_rows_t A, const float* Bm, long ldb, lidbox_rows_out_t C, int K, int N,
                               int epilogue, const float* aux, void* workspace, size_t workspace_bytes,
@@ -1384,11 +1226,8 @@ int tn_partial_launch(const char* fn, lidbox_rows_t A, lidbox_rows_t Bd, float* 
         return LIDBOX_OK;
     }
 #define LBX_TN(BM_, BN_) launch_tn_t<BM_, BN_>(al, grid, st, to_dev(A), to_dev(Bd), P, Pc, M, K1, N, tiles_n, ntiles, pl.rows_per_split)
-#if LBX_GEMM_BK == 16
     if (pl.bm == 128 && pl.bn == 128) LBX_TN(128, 128);
-    else
-#endif
-    if (pl.bm == 128) LBX_TN(128, 64);
+    else if (pl.bm == 128) LBX_TN(128, 64);
     else if (pl.bn == 128) LBX_TN(64, 128);
     else LBX_TN(64, 64);
 #undef LBX_TN
@@ -1512,7 +1351,7 @@ bool pair_plan(long M, int Co, int N, int K1, size_t ws_nt_bytes, size_t ws_tn_b
     const RowsChoice ch = choose_rows_env(1, M, N, Co, ws_nt_bytes);
     const TnPlan pl = tn_plan(M, K1, Co);
     const SkTn sk = sk_tn_plan(M, K1, Co);
-    const bool sk_rows = !getenv("LIDBOX_GEMM_PLAN") && !getenv("LIDBOX_GEMM_TILE") && lidbox_gemm_plan_is_stream_k(1, M, N, Co, ws_nt_bytes);
+    const bool sk_rows = !getenv("LIDBOX_GEMM_PLAN") && lidbox_gemm_plan_is_stream_k(1, M, N, Co, ws_nt_bytes);
     const bool sk_tn = sk.ok && !getenv("LIDBOX_GEMM_TN_PLAN") && !sk_tuned_out(2, M, Co, K1) && ws_tn_bytes >= sk.ws_need;
     const size_t tn_need = ((size_t)pl.splits * K1 * Co + (size_t)pl.splits * Co) * sizeof(float);
     const long rows_blocks = lbx_cdiv(M, 64L) * lbx_cdiv((long)N, 64L) * ch.splits;

@@ -31,16 +31,9 @@ constexpr int D16_ROW_BYTES = D16_BK * 2;   // 128
 // covering the 64 banks once when its 16 lanes hit 16 different 16-byte slots mod 256 bytes: slot = (row & 1) * 8 + position.
 // The 8 even (odd) rows of a group differ exactly in bits 1, 3, 4 of the row index, so THOSE bits are the key.  Round 3's
 // key, row & 7 (bits 0-2), assumed groups of 8 consecutive lanes: rows 12 and 20 (4 and 28, ...) of one group then share
-// key and parity -> every operand fetch was a 2-way bank conflict (LBX_D16_SWZ=0 rebuilds that layout: A/B aid).
-#ifndef LBX_D16_SWZ
-#define LBX_D16_SWZ 1
-#endif
+// key and parity -> every operand fetch was a 2-way bank conflict.
 __device__ __forceinline__ int d16_swz(int row) {
-#if LBX_D16_SWZ
     return ((row >> 1) & 1) | ((row >> 2) & 2) | ((row >> 2) & 4);
-#else
-    return row & 7;
-#endif
 }
 
 template <int ROWS>
@@ -202,16 +195,13 @@ __global__ __launch_bounds__(256, OCC) void gemm16s_rows_dma_kernel(RowsH A, Row
         ++cur;
         if (cur == STAGES) cur = 0;
     }
-#ifndef LBX_D16_WIDE_EPI
-#define LBX_D16_WIDE_EPI 1
-#endif
     // Epilogues that READ per element (ReLU mask, accumulate: the dgrads) take the 16-byte epilogue of the eight-wave tile
     // (gemm16_pp.h: pp_store_tile) through a wave-private strip of the ring -- frame5 / frame4 dgrad 30.6 -> 28.8 / 15.4 -> 12.9 us at
     // bs 256, 55.5 -> 49.2 / 26.7 -> 22.3 us at bs 512; store-only epilogues keep the row loop, which the other resident workgroups
     // hide and which costs no LDS round trip (forward launches were 1-5 us slower on the strip: profiles/r05_bf16_wide_epilogue_ab.txt)
     const bool reads = gridDim.y == 1 && (epi == LIDBOX_EPI_RELU_MASK || epi == LIDBOX_EPI_ACCUM_RELU_MASK || epi == LIDBOX_EPI_ACCUM ||
                                           epi == LIDBOX_EPI_ACCUM_RELU);
-    if constexpr (LBX_D16_WIDE_EPI && NJ == 2 && STAGES * ST >= 4 * D16_EPI_BYTES) {
+    if constexpr (NJ == 2 && STAGES * ST >= 4 * D16_EPI_BYTES) {
         if (reads) {
             // nobody reads the ring any more behind this barrier (the last step's DMAs were waited for before its own barrier)
             __builtin_amdgcn_s_barrier();

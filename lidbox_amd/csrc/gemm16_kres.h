@@ -26,9 +26,6 @@
 
 namespace {
 
-#ifndef LBX_KRES_ABLATE
-#define LBX_KRES_ABLATE 0                               // measurement builds only (wrong results): 1 no epilogue, 2 no MFMA loop, 4 no image DMA
-#endif
 constexpr int KRES_KMAX = 208;                        // contraction, rounded up to 16
 constexpr int KRES_BN = 64;
 constexpr int KRES_ROWS = 32;                         // rows of a unit
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(64 * KRES_WAVES, 3) void gemm16s_rows_kres_kernel(R
     int buf = 0;
     for (; u < nunits; u += ustep, buf ^= 1) {
         const int b = (int)(u / blocks), blk = (int)(u - (long)b * blocks);
-        if (!(LBX_KRES_ABLATE & 4) && u + ustep < nunits) issue_image(u + ustep, buf ^ 1);   // the other buffer's last reader was the previous unit's loop
+        if (u + ustep < nunits) issue_image(u + ustep, buf ^ 1);   // the other buffer's last reader was the previous unit's loop
         f32x16 acc[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
@@ -145,20 +142,19 @@ __global__ __launch_bounds__(64 * KRES_WAVES, 3) void gemm16s_rows_kres_kernel(R
 #pragma unroll
             for (int s = 0; s < NKS; ++s) read_ops(ai, bi_, s, a[s], bq[s]);
 #pragma unroll
-            for (int s = 0; s < ((LBX_KRES_ABLATE & 2) ? 1 : NKS); ++s)
+            for (int s = 0; s < NKS; ++s)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bq[s][j], acc[j], 0, 0, 0);
         } else {
             // operands of slice s + 1 are fetched before the MFMAs of slice s are issued
             bf16x8 a0, a1, b0[NJ], b1[NJ];
-            const int ns = (LBX_KRES_ABLATE & 2) ? 1 : nks;
             read_ops(ai, bi_, 0, a0, b0);
-            for (int s = 0; s < ns; s += 2) {
-                if (s + 1 < ns) read_ops(ai, bi_, s + 1, a1, b1);
+            for (int s = 0; s < nks; s += 2) {
+                if (s + 1 < nks) read_ops(ai, bi_, s + 1, a1, b1);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0[j], acc[j], 0, 0, 0);
-                if (s + 1 < ns) {
-                    if (s + 2 < ns) read_ops(ai, bi_, s + 2, a0, b0);
+                if (s + 1 < nks) {
+                    if (s + 2 < nks) read_ops(ai, bi_, s + 2, a0, b0);
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1[j], acc[j], 0, 0, 0);
                 }
@@ -167,13 +163,6 @@ __global__ __launch_bounds__(64 * KRES_WAVES, 3) void gemm16s_rows_kres_kernel(R
         __builtin_amdgcn_s_setprio(0);
         // the next image (it had the whole loop to land) and the previous unit's stores -- not this unit's, which go out below
         sk_wait_vm<0>();
-        if (LBX_KRES_ABLATE & 1) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc += acc[0][r] + acc[1][r];
-            if (sacc == 12345.f) C16[tid] = 1;
-            continue;
-        }
         const int t0 = KRES_ROWS * blk + erow;                 // this lane's first row inside the utterance
         const long rbase = (Cd.batch == 1 ? ((long)b * A.rpb + t0) * Cd.rs : (long)b * Cd.bs + (long)t0 * Cd.rs) + n0 + ecol;
 #pragma unroll

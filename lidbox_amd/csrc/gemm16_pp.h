@@ -81,17 +81,8 @@ __device__ __forceinline__ void pp_barrier() {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 }
-__device__ __forceinline__ void pp_loop_barrier();
 __device__ __forceinline__ void pp_wait_lds() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-#ifndef LBX_PP_ABLATE
-#define LBX_PP_ABLATE 0
-#endif
-__device__ __forceinline__ void pp_loop_barrier() {
-    if (LBX_PP_ABLATE & 8) __builtin_amdgcn_sched_barrier(0);
-    else pp_barrier();
 }
 
 // Epilogue of one wave's MI x NJ accumulator blocks through a wave-private LDS strip: a 32-row x (32 NJ)-column strip is
@@ -371,11 +362,6 @@ struct PpMaskPrefetch {
 // C[M,N] = epi(A[M,K] . B[N,K]^T), bf16 operands, fp32 accumulate; 512 threads, tile 256 x BN (BN = 256: waves 2 x 4, 128 x 64
 // each; BN = 128: waves 4 x 2, 64 x 64 each); grid.x = [carried reduce blocks] + tiles (XCD-chunk remapped), grid.y = K splits.
 // LDS: an A ring of THREE stages (3 x 32 KB) and a B ring of two (2 x BN x 128 B): 160 KB at BN = 256, the whole CU.
-// LBX_PP_ABLATE (measurement builds only, results are wrong): 1 = no LDS-DMA issue after the prologue, 2 = operand fetches of the
-// first sub-step only, 4 = no MFMAs, 8 = no barriers inside the loop, 16 = no epilogue, 32 = no DMA at all (with 1), 64 = no mask prefetch
-#ifndef LBX_PP_ABLATE
-#define LBX_PP_ABLATE 0
-#endif
 
 template <int BN>
 constexpr int pp_lds_bytes() {
@@ -421,16 +407,14 @@ __device__ __forceinline__ void pp_tile(const RowsH& A, const RowsH& Bw, const R
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // the dgrad epilogue's ReLU mask rides in the K loop when the wave's whole tile takes the epilogue's vector path
-    const bool mask_epi = gridDim.y == 1 && mask16 && (epi == LIDBOX_EPI_RELU_MASK || epi == LIDBOX_EPI_ACCUM_RELU_MASK);
-    PpMaskPrefetch<MI * 4> mp;
+    // the dgrad epilogue's ReLU mask could ride in the K loop when the wave's whole tile takes the epilogue's vector path.
     // Built, parity-green, and SLOWER (profiles/r05_bf16_pp_mask_prefetch_ab.txt: dgrads +4 ... +6 us at bs 512, the configs[4] step 1.091 vs
     // 1.070 ms): 16 row-offset divisions, 16 loads and ~400 fold instructions per lane and 28 more registers inside the K loop cost
-    // more than the 6 us of mask traffic they take out of the epilogue burst.  Compiled out (-DLBX_PP_MASK_PREFETCH=1 brings it back).
-#ifndef LBX_PP_MASK_PREFETCH
-#define LBX_PP_MASK_PREFETCH 0
-#endif
-    mp.init(LBX_PP_MASK_PREFETCH && !(LBX_PP_ABLATE & 64) && mask_epi && n >= 4 && m0 + rowA + 32 * MI <= M && n0 + rowB + 64 <= N && Cd.rs % 8 == 0 &&
+    // more than the 6 us of mask traffic they take out of the epilogue burst.  Switched off by the `false` below.  The dead code stays:
+    // without it hipcc allocates the registers of these kernels differently.
+    const bool mask_epi = gridDim.y == 1 && mask16 && (epi == LIDBOX_EPI_RELU_MASK || epi == LIDBOX_EPI_ACCUM_RELU_MASK);
+    PpMaskPrefetch<MI * 4> mp;
+    mp.init(false && mask_epi && n >= 4 && m0 + rowA + 32 * MI <= M && n0 + rowB + 64 <= N && Cd.rs % 8 == 0 &&
             (Cd.batch == 1 || Cd.bs % 8 == 0) && (((uintptr_t)mask16) & 15) == 0);
     PpPieces<NA> pa;
     PpPieces<NB> pb;
@@ -439,32 +423,16 @@ __device__ __forceinline__ void pp_tile(const RowsH& A, const RowsH& Bw, const R
     // A of step `step` into A stage step % 3, B of step `step` into B stage step & 1 (the lists advance with every issue: A runs
     // two steps ahead of the step being computed, B one)
     auto issue_a = [&](int step, int sa) {
-        if ((LBX_PP_ABLATE & 32) || ((LBX_PP_ABLATE & 1) && step > 1)) return;
         pa.issue_step(lds0 + (unsigned)(sa * A_ST), step == n - 1 ? ktail : D16_BK);
     };
     auto issue_b = [&](int step, int sb) {
-        if ((LBX_PP_ABLATE & 32) || ((LBX_PP_ABLATE & 1) && step > 0)) return;
         pb.issue_step(lds0 + (unsigned)(B_RING + sb * B_ST), step == n - 1 ? ktail : D16_BK);
     };
 
     auto body = [&](auto grp_tag) {
         constexpr int G = decltype(grp_tag)::value;
         bf16x8 a[MI][KH], b[NJ][KH];
-        bool first_load = true;
         auto load = [&](int sa, int sb, int j) {
-            if (LBX_PP_ABLATE & 2) {
-                if (!first_load) {
-#pragma unroll
-                    for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                        for (int bj = 0; bj < NJ; ++bj) asm volatile("" : "+v"(b[bj][kk]));
-#pragma unroll
-                        for (int bi = 0; bi < MI; ++bi) asm volatile("" : "+v"(a[bi][kk]));
-                    }
-                    return;
-                }
-                first_load = false;
-            }
             const char* sta = smem16p + sa * A_ST;
             const char* stb = smem16p + B_RING + sb * B_ST;
 #pragma unroll
@@ -476,16 +444,6 @@ __device__ __forceinline__ void pp_tile(const RowsH& A, const RowsH& Bw, const R
             }
         };
         auto comp = [&]() {
-            if (LBX_PP_ABLATE & 4) {
-#pragma unroll
-                for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                    for (int bj = 0; bj < NJ; ++bj) asm volatile("" ::"v"(b[bj][kk]));
-#pragma unroll
-                    for (int bi = 0; bi < MI; ++bi) asm volatile("" ::"v"(a[bi][kk]));
-                }
-                return;
-            }
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk)
@@ -528,7 +486,7 @@ __device__ __forceinline__ void pp_tile(const RowsH& A, const RowsH& Bw, const R
                     else sk_wait_vm<0>();
                     mp.fold();
                 }
-                pp_loop_barrier();
+                pp_barrier();
                 comp();
                 if (G == 0) {
                     if (j == SUB - 1 && more_b) {
@@ -536,9 +494,9 @@ __device__ __forceinline__ void pp_tile(const RowsH& A, const RowsH& Bw, const R
                         else sk_wait_vm<0>();
                         mp.fold();
                     }
-                    pp_loop_barrier();
+                    pp_barrier();
                 } else if (!(j == SUB - 1 && !more_b)) {
-                    pp_loop_barrier();
+                    pp_barrier();
                 }
             }
             sa = sa + 1 == 3 ? 0 : sa + 1;
@@ -550,17 +508,6 @@ __device__ __forceinline__ void pp_tile(const RowsH& A, const RowsH& Bw, const R
 
     // epilogue through this wave's LDS strip: no wave reads a stage any more once group 0 has passed the last barrier (group
     // 1's last sub-step runs from registers), and no DMA is in flight
-    if (LBX_PP_ABLATE & 16) {                                  // no epilogue: one store per wave keeps the accumulators alive
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-        if (sacc == 12345.f) P[tid] = sacc;
-        return;
-    }
     pp_store_tile<MI, NJ>(acc, reinterpret_cast<float*>(smem16p + wv * PP_EPI_BYTES), m0 + rowA, n0 + rowB, lane, m_beg, M, N, epi, aux, Cd, P,
                           split, C16, mask16, mp.bits, mp.complete());
 }

@@ -27,10 +27,6 @@ namespace {
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_pp;
 
-#ifndef LBX_PPT_ABLATE
-#define LBX_PPT_ABLATE 0                                // measurement builds only (wrong results): 1 no DMA after the prologue, 2 operand fetches
-#endif                                                  // of the first step only, 4 no MFMAs, 16 no epilogue, 32 every step fetches the same rows, 64 DMA addresses but no DMA, 128 no column sums
-
 constexpr int PPT_BM = 32;                            // contraction rows per K step (= per LDS stage)
 constexpr int PPT_BT = 256;                           // tile edge (K1 and N)
 constexpr int PPT_ROW_BYTES = PPT_BT * 2;             // 512
@@ -77,9 +73,7 @@ struct PptStream {
 #pragma unroll
         for (int i = 0; i < PPT_NP; ++i) {
             const unsigned off = (unsigned)(wv * PPT_NP + i) * 1024u;
-            if (LBX_PPT_ABLATE & 64) {                                 // addresses only
-                asm volatile("" ::"v"(va[i]), "v"(vb[i]), "s"(sta + off));
-            } else if (tail) {
+            if (tail) {
                 const bool in = m + 2 * i < mend;
                 sk_dma_f(in ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sa) + va[i]) : g_sk_zero, sta + off);
                 sk_dma_f(in ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sb) + vb[i]) : g_sk_zero, stb + off);
@@ -88,7 +82,6 @@ struct PptStream {
                 sk_dma_s(sb, vb[i], stb + off);
             }
         }
-        if (LBX_PPT_ABLATE & 32) return;                               // the same rows every step: L2 hits
         m += PPT_BM;
 #pragma unroll
         for (int i = 0; i < PPT_NP; ++i) {
@@ -158,7 +151,6 @@ __global__ __launch_bounds__(512, 2) void gemm16s_tn_pp_kernel(RowsH A, RowsH Bd
     PptStream ps;
     ps.init(A, Bd, mbeg, i0, K1, n0, N, lane, wv);
     auto issue = [&](int step, int stage) {
-        if ((LBX_PPT_ABLATE & 1) && step >= D - 1) return;
         ps.issue_step(lds0 + (unsigned)(stage * PPT_ST), lds0 + (unsigned)(B_RING + stage * PPT_ST), wv, mend, ragged && step == n - 1);
     };
 
@@ -178,21 +170,7 @@ __global__ __launch_bounds__(512, 2) void gemm16s_tn_pp_kernel(RowsH A, RowsH Bd
     auto body = [&](auto grp_tag) {
         constexpr int G = decltype(grp_tag)::value;
         bf16x8 a[MI][KH], b[NJ][KH];
-        bool first_load = true;
         auto load = [&](int stage) {
-            if (LBX_PPT_ABLATE & 2) {
-                if (!first_load) {
-#pragma unroll
-                    for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                        for (int bj = 0; bj < NJ; ++bj) asm volatile("" : "+v"(b[bj][kk]));
-#pragma unroll
-                        for (int bi = 0; bi < MI; ++bi) asm volatile("" : "+v"(a[bi][kk]));
-                    }
-                    return;
-                }
-                first_load = false;
-            }
             const char* st = smem16q + stage * PPT_ST;
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk) {
@@ -203,16 +181,6 @@ __global__ __launch_bounds__(512, 2) void gemm16s_tn_pp_kernel(RowsH A, RowsH Bd
             }
         };
         auto comp = [&]() {
-            if (LBX_PPT_ABLATE & 4) {
-#pragma unroll
-                for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                    for (int bj = 0; bj < NJ; ++bj) asm volatile("" ::"v"(b[bj][kk]));
-#pragma unroll
-                    for (int bi = 0; bi < MI; ++bi) asm volatile("" ::"v"(a[bi][kk]));
-                }
-                return;
-            }
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk) {
@@ -221,7 +189,7 @@ __global__ __launch_bounds__(512, 2) void gemm16s_tn_pp_kernel(RowsH A, RowsH Bd
 #pragma unroll
                     for (int bj = 0; bj < NJ; ++bj)
                         acc[bi][bj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[bi][kk], b[bj][kk], acc[bi][bj], 0, 0, 0);
-                if (do_csum && !(LBX_PPT_ABLATE & 128)) csacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, wm ? b[1][kk] : b[0][kk], csacc, 0, 0, 0);
+                if (do_csum) csacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, wm ? b[1][kk] : b[0][kk], csacc, 0, 0, 0);
             }
             __builtin_amdgcn_s_setprio(0);
         };
@@ -254,17 +222,6 @@ __global__ __launch_bounds__(512, 2) void gemm16s_tn_pp_kernel(RowsH A, RowsH Bd
     if (grp == 0) body(IntTag<0>{});
     else body(IntTag<1>{});
 
-    if (LBX_PPT_ABLATE & 16) {
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-        if (sacc == 12345.f) P[tid] = sacc;
-        return;
-    }
     // raw sums to P[split][i][n] through this wave's LDS strip (no wave reads a stage any more, no DMA is in flight)
     const RowsOutD none{nullptr, 0, (long)N, 1, K1};
     const unsigned nobits[MI] = {};

@@ -54,12 +54,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef LBX16_TAIL_MIN_ROUNDS
-#define LBX16_TAIL_MIN_ROUNDS 1
-#endif
-#ifndef LBX16_TAIL_MIN_K
-#define LBX16_TAIL_MIN_K 1024              // tail split of the rows launches: measured a loss at K = 512 (bs 256), a gain at K >= 1500
-#endif
+constexpr int TAIL_MIN_ROUNDS = 1;
+constexpr int TAIL_MIN_K = 1024;           // tail split of the rows launches: measured a loss at K = 512 (bs 256), a gain at K >= 1500
 constexpr int BK = 32;        // contraction depth of one LDS tile
 constexpr int BT = 128;       // tile rows (M side) = tile columns (N side)
 constexpr int LDT = 40;       // LDS row stride in bf16: 32 + 8 pad = 80 bytes
@@ -399,10 +395,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_tn_kernel(RowsD A, RowsD Bd, fl
 // ------------------------------------------------------------------------------------------------
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef LBX16S_BK
-#define LBX16S_BK 64                        // K depth of one LDS tile of the storage kernel: 64 bf16 = one 128-byte line per row
-#endif
-constexpr int BKS = LBX16S_BK;
+constexpr int BKS = 64;                     // K depth of one LDS tile of the storage kernel: 64 bf16 = one 128-byte line per row
 constexpr int LDS_S = BKS + 8;              // LDS row stride in bf16 (80 or 144 bytes: conflict-free ds_read_b128 / ds_write_b128)
 constexpr int TILE_S = BT * LDS_S;
 constexpr int OCT = BKS / 8;                // 16-byte pieces per tile row (4 or 8 lanes cover one row)
@@ -494,13 +487,8 @@ __device__ __forceinline__ void mma_tile16s(const __bf16* As, const __bf16* Bs, 
     __builtin_amdgcn_s_setprio(0);
 }
 
-#ifndef LBX16S_DEPTH
-#define LBX16S_DEPTH 2                      // operand tiles in flight per workgroup (register ring)
-#endif
-#ifndef LBX16S_WAVES
-#define LBX16S_WAVES (LBX16S_BK == 64 ? 2 : 3)   // waves per SIMD: 73 KB of LDS per workgroup at BKS = 64 (2 per CU), 40 KB at 32 (3)
-#endif
-__global__ __launch_bounds__(256, LBX16S_WAVES) void gemm16s_rows_kernel(RowsH A, RowsH Bw, RowsOutD Cd, unsigned short* __restrict__ C16,
+constexpr int WAVES_S = 2;                  // waves per SIMD: 73 KB of LDS per workgroup (2 per CU)
+__global__ __launch_bounds__(256, WAVES_S) void gemm16s_rows_kernel(RowsH A, RowsH Bw, RowsOutD Cd, unsigned short* __restrict__ C16,
                                                               float* __restrict__ P, long m_beg, long M, int K, int N, int epi,
                                                               const float* __restrict__ aux, int tiles_n, unsigned ntiles,
                                                               int k_per_split, const unsigned short* __restrict__ mask16, ReduceJobs rj) {
@@ -529,9 +517,9 @@ __global__ __launch_bounds__(256, LBX16S_WAVES) void gemm16s_rows_kernel(RowsH A
     f32x16 acc[2][2];
     zero_acc(acc);
 
-    // register ring of depth LBX16S_DEPTH: while tile kt is multiplied out of LDS, tiles kt+1 .. kt+DEPTH-1 sit in registers
-    // and the loads of tile kt+DEPTH are issued (16 VGPRs per tile in flight)
-    constexpr int D = LBX16S_DEPTH;
+    // register ring of depth D = 2: while tile kt is multiplied out of LDS, tile kt+1 sits in registers and the loads of
+    // tile kt+2 are issued (16 VGPRs per tile in flight)
+    constexpr int D = 2;
     TileS ra[D], rb[D];
     const int nk = (kend - kbeg + BKS - 1) / BKS;
     auto fetch = [&](TileS& a, TileS& b, int t) {
@@ -558,9 +546,7 @@ __global__ __launch_bounds__(256, LBX16S_WAVES) void gemm16s_rows_kernel(RowsH A
     }
     for (int kt = 0; kt < nk;) {
         LBX16S_STEP(0)
-        if (D > 1 && kt < nk) LBX16S_STEP(1 % D)
-        if (D > 2 && kt < nk) LBX16S_STEP(2 % D)
-        if (D > 3 && kt < nk) LBX16S_STEP(3 % D)
+        if (kt < nk) LBX16S_STEP(1)
     }
 #undef LBX16S_STEP
     store_rows_tile<2, 2, true>(acc, m0, n0, wm, wn, lane, m_beg, M, N, epi, aux, Cd, P, split, 0ull, false, C16, mask16);
@@ -586,11 +572,8 @@ namespace {
 // lands on 4 disjoint quarters of the 256-byte bank row (320 = 64 mod 256).
 // The bias gradient (column sums of B) is summed in fp32 from the bf16 shadow's values.
 // ------------------------------------------------------------------------------------------------
-#ifndef LBX16T_LDS
-#define LBX16T_LDS 160                      // LDS row stride of the wgrad tiles, in bf16
-#endif
 constexpr int BKT = 64;                     // contraction rows of one LDS tile
-constexpr int LDS_T = LBX16T_LDS;
+constexpr int LDS_T = 160;                  // LDS row stride of the wgrad tiles, in bf16
 constexpr int TILE_T = BKT * LDS_T;
 
 struct TileT {
@@ -906,7 +889,6 @@ Rows16Plan plan_rows16(long M, int N, int K, size_t ws_bytes, int BK = 32) {
     const long max_s = K / (2 * BK);                 // at least two K-steps per split
     if (s > max_s) s = max_s;
     if (s > 64) s = 64;
-    if (const char* e = getenv("LIDBOX_GEMM16_SPLITS")) { const long v = atol(e); if (v >= 1) s = v < max_s ? v : (max_s > 1 ? max_s : 1); }   // tuning aid
     while (s > 1 && (size_t)s * M * N * sizeof(float) > ws_bytes) --s;
     if (s <= 1) return best;
     const int kps = (int)(lbx_cdiv(lbx_cdiv(K, s), BK) * BK);
@@ -927,11 +909,9 @@ Tn16Plan plan_tn16(long M, int K1, int N, int BK = 32) {
     // outweighs filling the second workgroup slot of every CU: measured on the storage kernel, frame1 (8 tiles) 58 -> 52 us and
     // frame4 (16 tiles) 25 -> 22 us with one round of 256 instead of 512 workgroups (profiles/r02_bf16_storage_wgrad.txt)
     if (BK == 64 && tiles <= 16) target = NUM_CU;
-    if (const char* e = getenv("LIDBOX_GEMM16_TN_SLOTS")) { const long v = atol(e); if (v >= 1) target = v; }   // tuning aid
     long s = target / tiles;                         // whole rounds only: one workgroup too many costs a full round
     const long max_s = lbx_cdiv(M, 4 * BK);          // at least four K-steps per slice
     if (s > max_s) s = max_s;
-    if (const char* e = getenv("LIDBOX_GEMM16_TN_SPLITS")) { const long v = atol(e); if (v >= 1) s = v; }                                 // tuning aid
     if (s < 1) s = 1;
     const long rps = lbx_cdiv(lbx_cdiv(M, s), BK) * BK;
     return Tn16Plan{(int)lbx_cdiv(M, rps), rps};
@@ -954,7 +934,6 @@ TnPpPlan plan_tn16_pp(long M, int K1, int N) {
     long s = NUM_CU / tiles;
     const long max_s = lbx_cdiv(M, 4 * PPT_BM);      // at least four K steps per slice
     if (s > max_s) s = max_s;
-    if (const char* e = getenv("LIDBOX_GEMM16_TN_PP_SPLITS")) { const long v = atol(e); if (v >= 1) s = v; }
     if (s < 1) s = 1;
     pl.rows_per_split = lbx_cdiv(lbx_cdiv(M, s), PPT_BM) * PPT_BM;
     pl.splits = (int)lbx_cdiv(M, pl.rows_per_split);
@@ -1002,14 +981,13 @@ int launch_rows16(const char* fn, lidbox_rows_t A, const float* Bm, long ldb, li
     // runs at the pace of a full one.  When the tiles beyond the last whole round are few (<= a quarter round), the
     // launch covers the row prefix that is a whole number of rounds and the few remaining rows go to a second launch
     // split along K (each of its workgroups does 1/splits of a tile, so it costs a fraction of a round).
-    static const bool no_tail_split = getenv("LIDBOX_GEMM16_NO_TAIL_SPLIT") != nullptr;      // A/B aid
     const long slots = 2 * NUM_CU;
     const long tiles = lbx_cdiv(M, BT) * tiles_n;
-    if (!no_tail_split && pl.splits == 1 && tiles > slots && K >= LBX16_TAIL_MIN_K) {   // short K: the extra launch costs more than the round
+    if (pl.splits == 1 && tiles > slots && K >= TAIL_MIN_K) {   // short K: the extra launch costs more than the round
         const long rounds = tiles / slots, rem_tiles = tiles - rounds * slots;
         const long main_tiles_m = rounds * slots / tiles_n;
         const long m_main = main_tiles_m * BT, m_rem = M - m_main;
-        if (rounds >= LBX16_TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
+        if (rounds >= TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
             const Rows16Plan rp = plan_rows16(m_rem, N, K, ws ? ws_bytes : 0);
             if (rp.splits > 1) {
                 if (int rc = launch_range(0, m_main, pl)) return rc;
@@ -1054,14 +1032,9 @@ Dma16Choice choose_dma16(long M, int N, int K, size_t ws_bytes, bool writes_fp32
         // contractions (frame1: K = 200, four steps under a 256 x 256 epilogue) and on launches of a quarter round (M = 8 448).
         const long t256 = lbx_cdiv(M, 256L) * lbx_cdiv((long)N, 256L);
         const long r256 = lbx_cdiv(t256, (long)NUM_CU);
-        bool no_pp = getenv("LIDBOX_GEMM16S_NO_PP") != nullptr;                       // A/B aid
-        if (const char* e = getenv("LIDBOX_GEMM16S_NO_PP_SHAPE")) {                   // A/B aid: "M,N,K" of one launch to keep off the tile
-            long em = 0; int en = 0, ek = 0;
-            if (sscanf(e, "%ld,%d,%d", &em, &en, &ek) == 3 && em == M && en == N && ek == K) no_pp = true;
-        }
         // (a launch that writes fp32 -- frame5's forward, 4 or 6 bytes per element -- pays a 256 x 256 epilogue twice over
         // in a 1.5-round launch: bs 512 62 vs 57 us; it stays on the small tiles unless the contraction is long)
-        if (!no_pp && !(writes_fp32 && K < 1024 && t256 > NUM_CU) &&
+        if (!(writes_fp32 && K < 1024 && t256 > NUM_CU) &&
             ((K >= 512 && 4 * t256 >= 3 * r256 * NUM_CU) || (K >= 1500 && 2 * t256 >= r256 * NUM_CU))) {
             c.bm = 256; c.bn = 256; c.stages = 2;
             c.splits = 1;
@@ -1251,7 +1224,6 @@ int launch_rows16s(const char* fn, lidbox_rows_t A, const void* B16, long ldb, l
                 long nstreams = NUM_CU / tiles_n;                               // one workgroup per CU (146 KB of LDS)
                 if (nstreams > lbx_cdiv(nunits, (long)KRES_WAVES)) nstreams = lbx_cdiv(nunits, (long)KRES_WAVES);
                 if (nstreams < 1) nstreams = 1;
-                if (const char* e = getenv("LIDBOX_GEMM16S_KRES_STREAMS")) { const long q = atol(e); if (q >= 1) nstreams = q; }   // tuning aid
                 g16_last_variant[0] = 1; g16_last_variant[1] = KRES_BN; g16_last_variant[2] = 1;      // {1, 64, 1}: the K-resident kernel
                 if ((K + 15) / 16 == 13)                                        // frame1 of the x-vector: K = 200
                     hipLaunchKernelGGL(gemm16s_rows_kres_kernel<13>, dim3((unsigned)(tiles_n * nstreams)), dim3(64 * KRES_WAVES), KRES_LDS_BYTES, st, Ah_,
@@ -1303,15 +1275,13 @@ int launch_rows16s(const char* fn, lidbox_rows_t A, const void* B16, long ldb, l
         }
         return LIDBOX_OK;
     };
-    static const bool no_tail_split = getenv("LIDBOX_GEMM16_NO_TAIL_SPLIT") != nullptr;
-    static const long slots_per_cu = getenv("LIDBOX_GEMM16S_SLOTS") ? atol(getenv("LIDBOX_GEMM16S_SLOTS")) : LBX16S_WAVES;   // tuning aid
-    const long slots = slots_per_cu * NUM_CU;
+    const long slots = (long)WAVES_S * NUM_CU;
     const long tiles = lbx_cdiv(M, BT) * tiles_n;
-    if (!no_tail_split && pl.splits == 1 && tiles > slots && K >= LBX16_TAIL_MIN_K) {
+    if (pl.splits == 1 && tiles > slots && K >= TAIL_MIN_K) {
         const long rounds = tiles / slots, rem_tiles = tiles - rounds * slots;
         const long main_tiles_m = rounds * slots / tiles_n;
         const long m_main = main_tiles_m * BT, m_rem = M - m_main;
-        if (rounds >= LBX16_TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
+        if (rounds >= TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
             const Rows16Plan rp = plan_rows16(m_rem, N, K, ws ? ws_bytes : 0, BKS);
             if (rp.splits > 1) {
                 if (int rc = launch_range(0, m_main, pl)) return rc;
@@ -1424,7 +1394,6 @@ extern "C" int lidbox_gemm_bf16s_nt_pair_carry(lidbox_rows_t A0, const void* B0,
                                                lidbox_stream_t stream) {
     g16_last_pair = 0;
     const Nt16Call c0{A0, B0, ldb0, C0, C16_0, K0, N0, epilogue0, aux0}, c1{A1, B1, ldb1, C1, C16_1, K1, N1, epilogue1, aux1};
-    static const bool off = getenv("LIDBOX_GEMM16S_NO_PAIR") != nullptr;                       // A/B aid
     PpProblem p0, p1;
     ReduceJob js[MAX_CARRY];
     int m = 0;
@@ -1436,7 +1405,7 @@ extern "C" int lidbox_gemm_bf16s_nt_pair_carry(lidbox_rows_t A0, const void* B0,
         if ((const void*)js[m].P == workspace || js[m].splits < 0) { jobs_ok = false; break; }
         ++m;
     }
-    if (!off && jobs_ok && getenv("LIDBOX_GEMM_NO_CARRY") == nullptr && aligned16(workspace) &&
+    if (jobs_ok && getenv("LIDBOX_GEMM_NO_CARRY") == nullptr && aligned16(workspace) &&
         pp2_problem(c0, workspace ? workspace_bytes : 0, &p0) && pp2_problem(c1, workspace ? workspace_bytes : 0, &p1)) {
         ReduceJobs rj;
         if (m > 0) rj = pack_carry(js, m, carry_cap16());

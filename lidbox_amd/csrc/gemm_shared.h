@@ -60,9 +60,6 @@ template <int V>
 struct IntTag {
     static constexpr int value = V;
 };
-#ifndef LBX_EPI_INNER
-#define LBX_EPI_INNER 1            // 0: A/B aid (every block through the predicated epilogue)
-#endif
 
 // Epilogue of one workgroup tile held as MI x NJ accumulator blocks per wave (waves 2 x 2).
 // Rows of this launch are [m_beg, M).  gridDim.y > 1 = split along K: raw partial sums go to
@@ -170,7 +167,7 @@ __device__ __forceinline__ void store_rows_tile(const f32x16 (&acc)[MI][NJ], lon
             constexpr int bi = decltype(bi_tag)::value;
             const long rb0 = m0 + wm * (32 * MI) + bi * 32;                 // the block's first row (wave-uniform)
             const long wrap_u = batched ? Cd.bs - (long)Cd.rpb * Cd.rs : 0;
-            const bool inner = LBX_EPI_INNER && rb0 + 32 <= M && n0 + wn * (32 * NJ) + 32 * NJ <= N && (!batched || (unsigned)Cd.rpb >= 28) &&
+            const bool inner = rb0 + 32 <= M && n0 + wn * (32 * NJ) + 32 * NJ <= N && (!batched || (unsigned)Cd.rpb >= 28) &&
                                out_rs > 0 && out_rs < (1L << 25) && wrap_u >= 0 && wrap_u < (1L << 30);
             if (!inner) { fast_block(FarTag<false>{}, FarTag<false>{}, bi_tag); return; }
             const bool nowrap = !batched || (unsigned)rb0 % (unsigned)Cd.rpb + 32u <= (unsigned)Cd.rpb;
@@ -235,7 +232,8 @@ __device__ __forceinline__ void store_rows_tile(const f32x16 (&acc)[MI][NJ], lon
                     const int r = r0 + i;
                     float x = acc[bi][bj][r] + bias[bj];
                     if (has_mask) {
-                        // have_mask_bits: the caller read the mask during its K loop; bit (bi*NJ + bj)*16 + r
+                        // have_mask_bits: the caller read the mask during its K loop; bit (bi*NJ + bj)*16 + r.  No caller does since the
+                        // measured-slower K-loop prefetch left gemm.hip, but dropping the parameters changes the code hipcc emits
                         const bool keep = have_mask_bits ? ((mask_bits >> ((bi * NJ + bj) * 16 + r)) & 1ull) != 0 : mv[i] > 0.f;
                         x = keep ? x : 0.f;
                     }
@@ -259,7 +257,7 @@ __device__ __forceinline__ void store_rows_tile(const f32x16 (&acc)[MI][NJ], lon
             constexpr int bi = decltype(bi_tag)::value;
             const long rb0 = m0 + wm * (32 * MI) + bi * 32;                 // the block's first row (wave-uniform)
             const long wrap_u = batched ? Cd.bs - (long)Cd.rpb * Cd.rs : 0;
-            const bool inner = LBX_EPI_INNER && !decltype(far_tag)::value && rb0 + 32 <= M && n0 + wn * (32 * NJ) + 32 * NJ <= N &&
+            const bool inner = !decltype(far_tag)::value && rb0 + 32 <= M && n0 + wn * (32 * NJ) + 32 * NJ <= N &&
                                out_rs > 0 && out_rs < (1L << 25) && wrap_u >= 0 && wrap_u < (1L << 30);
             if (inner) block(far_tag, FarTag<true>{}, bi_tag);
             else block(far_tag, FarTag<false>{}, bi_tag);
@@ -284,7 +282,7 @@ __device__ __forceinline__ void store_partial_blocks(float* __restrict__ Pd, con
 #pragma unroll
         for (int bi = 0; bi < MI; ++bi) {
             const int rb = i0 + wm * (32 * MI) + bi * 32;
-            if (LBX_EPI_INNER && rb + 32 <= K1 && cb + 32 <= N) {
+            if (rb + 32 <= K1 && cb + 32 <= N) {
                 float* p = Pd + (long)(rb + 4 * h) * N + col;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) p[(long)((r & 3) + 8 * (r >> 2)) * N] = acc[bi][bj][r];

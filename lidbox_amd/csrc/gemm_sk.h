@@ -36,17 +36,8 @@ namespace {
 
 constexpr int SK_BM = 128, SK_BN = 128, SK_BK = 16;
 constexpr int SK_A_STAGE = SK_BM * SK_BK, SK_B_STAGE = SK_BK * SK_BN, SK_STAGE = SK_A_STAGE + SK_B_STAGE;   // floats
-#ifndef LBX_SK_STAGES
-#define LBX_SK_STAGES 3
-#endif
-#ifndef LBX_SK_WGCU
-#define LBX_SK_WGCU 3
-#endif
-#ifndef LBX_SK_PRIO_ROTATE
-#define LBX_SK_PRIO_ROTATE 1               // 0: leave the arbitration to age (A/B aid)
-#endif
-constexpr int SK_STAGES = LBX_SK_STAGES;          // LDS ring depth: 48 KB per workgroup, three workgroups per CU
-constexpr int SK_WGCU = LBX_SK_WGCU;              // resident workgroups per CU the persistent grid is sized for
+constexpr int SK_STAGES = 3;                      // LDS ring depth: 48 KB per workgroup, three workgroups per CU
+constexpr int SK_WGCU = 3;                        // resident workgroups per CU the persistent grid is sized for
 constexpr int SK_SLAB = SK_BM * SK_BN;            // floats of one partial tile
 constexpr size_t SK_COUNTER_BYTES = 16384;        // head of the workspace: one arrival counter per streamed tile (<= 4096)
 constexpr size_t SK_LDS_BYTES = (size_t)SK_STAGES * SK_STAGE * sizeof(float);
@@ -249,7 +240,7 @@ __device__ __forceinline__ void sk_kloop(float* smem, unsigned lds0, int wv, int
         int tgt = cur + STAGES - 1;
         if (tgt >= STAGES) tgt -= STAGES;
         const float* st = smem + cur * SK_STAGE;
-        if (WGCU > 0 && LBX_SK_PRIO_ROTATE) {
+        if (WGCU > 0) {
             if ((unsigned)(t + prio_slot) % (unsigned)(WGCU > 0 ? WGCU : 1) == 0) __builtin_amdgcn_s_setprio(2);
             else __builtin_amdgcn_s_setprio(0);
         }
@@ -295,7 +286,7 @@ __device__ __forceinline__ void sk_kloop(float* smem, unsigned lds0, int wv, int
         step_end();
         cur = nxt;
     }
-    if (WGCU > 0 && LBX_SK_PRIO_ROTATE) __builtin_amdgcn_s_setprio(0);
+    if (WGCU > 0) __builtin_amdgcn_s_setprio(0);
 }
 
 // partial tile <-> slab, accumulator order: [(wave * 4 + block) * 4 + r4][lane][4] -- 1 KB per wave access.

@@ -20,7 +20,6 @@
 // the data (speech frames per utterance) are returned as counters, the host sizes the next buffer from them
 // exactly as the reference's eager tensors do.  No atomics on floats: results are deterministic.
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -589,8 +588,7 @@ extern "C" int lidbox_snr_mixer(const float* clean, const float* noise, const fl
     if (B == 0) return LIDBOX_OK;
     const bool vec = N % 4 == 0 && ((((uintptr_t)clean) | ((uintptr_t)noise) | ((uintptr_t)clean_norm) |
                                      ((uintptr_t)noise_new) | ((uintptr_t)noisy)) & 15) == 0;
-    static const bool no_reg = getenv("LIDBOX_SNR_NO_REG") != nullptr;            // A/B aid
-    if (vec && !no_reg && N <= 1024L * 4 * 8) {
+    if (vec && N <= 1024L * 4 * 8) {
         // whole pair in registers: 4 or 8 float4 per thread and signal (16 would spill at the 128-VGPR limit of a
         // 1024-thread workgroup); longer pairs take the three-pass kernel
         hipStream_t st = (hipStream_t)stream;

@@ -255,8 +255,6 @@ class Trainer:
         # it (SequentialTDNN.fused_output_ok); LIDBOX_NO_FUSED_OUTPUT=1 keeps the nine separate launches (A/B aid)
         import os as _os
         self.fuse_output = self.loss_kind == "nll" and _os.environ.get("LIDBOX_NO_FUSED_OUTPUT") != "1" and model.fused_output_ok()
-        if _os.environ.get("LIDBOX_OVERLAP_WGRAD") is not None:          # A/B aid
-            overlap_wgrad = _os.environ["LIDBOX_OVERLAP_WGRAD"] == "1"
         if overlap_wgrad and model.wgrad_stream is None:
             model.wgrad_stream = torch.cuda.Stream(device=self.device)
         # overlap_head_wgrad: only the dense head's wgrads (a few workgroups each, M = batch) on a second stream, beside the
@@ -358,7 +356,7 @@ class Trainer:
             D = out.shape[1]
             zn, dzn, per = self._ap_buffers(ws, D)
             want_scores = self.metric is not None and not self._warming
-            if D <= 4096 and not os.environ.get("LIDBOX_AP_SEPARATE"):
+            if D <= 4096:
                 # normalise -> loss + gradient -> gradient through the normalisation -> predict() scores: one launch
                 nv.check(lib.lidbox_ap_head_fwd_bwd(nv.ptr(out), nv.ptr(labels), B, D, self.ap.N, self.ap.delta_weight, scale, None,
                                                     nv.ptr(per), nv.ptr(ws.dh[-1]), nv.ptr(ws.ap_scores) if want_scores else None, st))
@@ -400,7 +398,7 @@ class Trainer:
         m = self.model
         if self.feature is None or not m.bf16_storage or m.frontend or ws.act16[0] is None:
             return False
-        if self.feature.get("cmvn") or m.channel_dropout_rate > 0 or os.environ.get("LIDBOX_FEAT_NO_SHADOW"):    # env: A/B aid
+        if self.feature.get("cmvn") or m.channel_dropout_rate > 0:
             return False
         in_ptr, _, _, _ = ws.input_target()
         return (in_ptr.value - ws.act[0].data_ptr()) % 16 == 0 and ws.act16[0].data_ptr() % 8 == 0
@@ -474,7 +472,7 @@ class Trainer:
         for i in range(hi_edges[k] - 1, lo_edges[k] - 1, -1):
             self.model.backward_conv_ws(ws, i)
         self._prepared = False
-        if k == self.num_stages - 1 and not self._warming and self.opt["cls"] == "Adam" and not os.environ.get("LIDBOX_ADAM_PREPARE_LAUNCH"):
+        if k == self.num_stages - 1 and not self._warming and self.opt["cls"] == "Adam":
             # the optimizer's scalar half (step counter, bias-corrected rate) rides in the launch that finishes the last wgrad
             job = nv.ReduceJob()
             o = self.opt
@@ -612,18 +610,16 @@ class Trainer:
                                   "host-launched collectives between graph segments" % (type(exc).__name__, exc))
                     self.sync._pending.clear()
                     torch.cuda.synchronize(self.device)
-                    adam_seg = self._capture(segs[-1]).replay if os.environ.get("LIDBOX_ADAM_GRAPH") else segs[-1]
-                    entry["graphs"] = tuple(self._capture(seg).replay for seg in segs[:-1]) + (adam_seg,)
+                    entry["graphs"] = tuple(self._capture(seg).replay for seg in segs[:-1]) + (segs[-1],)
                     self.grad_sync_mode = "segmented"
             elif self.sync.active:
-                # the optimizer segment is two small kernels behind the last collective: launched directly unless
-                # LIDBOX_ADAM_GRAPH is set (a graph launch costs more than it saves there)
+                # the optimizer segment is two small kernels behind the last collective: launched directly (a graph launch
+                # costs more than it saves there)
                 if os.environ.get("LIDBOX_REQUIRE_INGRAPH_SYNC"):
                     raise RuntimeError("LIDBOX_REQUIRE_INGRAPH_SYNC is set but the gradient exchange of this step cannot be captured "
                                        "(backend %r, LIDBOX_SEGMENTED_SYNC=%r)" % (self.sync.dist.get_backend(self.sync.group),
                                                                                   os.environ.get("LIDBOX_SEGMENTED_SYNC")))
-                adam_seg = self._capture(segs[-1]).replay if os.environ.get("LIDBOX_ADAM_GRAPH") else segs[-1]
-                entry["graphs"] = tuple(self._capture(seg).replay for seg in segs[:-1]) + (adam_seg,)
+                entry["graphs"] = tuple(self._capture(seg).replay for seg in segs[:-1]) + (segs[-1],)
                 self.grad_sync_mode = "segmented"
             else:
                 entry["graphs"] = (self._capture(lambda: [seg() for seg in segs]).replay,)

@@ -1,21 +1,15 @@
 """ISA census of feat512_stream_kernel<2, true, false, false, 13> (the log-mel instantiation of the train step) from hipcc's device assembly.
 
-    python tools/feat_census.py [--timing]      (build container or GPU box: needs hipcc only)
+    python tools/feat_census.py      (build container or GPU box: needs hipcc only)
 
 Compiles csrc/features.hip to gfx950 assembly, cuts the kernel into basic blocks, and counts instructions by class per
-block.  With --timing the kernel is built with -DLBX_FEAT_TIMING=0, whose s_memtime stamps mark the phase boundaries of a
-tile (load+window | pass-1 DFT | twiddle | exchange | pass-2 DFT | untangle | mel | store): the counts between two stamps
-are the phase's instructions (the stamped build's code is the production code plus the stamps).
-Static counts of straight-line blocks; a block inside a loop is annotated with its label so that trip counts can be applied
+block.  Static counts of straight-line blocks; a block inside a loop is annotated with its label so that trip counts can be applied
 by hand (the mel run loop: ceil(seg_len / 4) trips; the shuffle-combine loop: seg_steps trips)."""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-timing = "--timing" in sys.argv
-out = "/tmp/feat_census%s.s" % ("_t" if timing else "")
+out = "/tmp/feat_census.s"
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
        "-I" + os.path.join(ROOT, "lidbox_amd", "csrc"), "--cuda-device-only", "-S", os.path.join(ROOT, "lidbox_amd", "csrc", "features.hip"), "-o", out]
-if timing:
-    cmd.insert(1, "-DLBX_FEAT_TIMING=0")
 subprocess.run(cmd, check=True, capture_output=True)
 NW = next((a.split("=")[1] for a in sys.argv if a.startswith("--nw=")), "4")        # --nw=14: the wide workgroup's instantiation
 KERNEL = "_ZN12_GLOBAL__N_121feat512_stream_kernelILi2ELb1ELb0ELb0ELi13EEEvNS_9FusedArgsE"
@@ -42,7 +36,6 @@ def klass(op):
     if op.startswith(("global_store", "buffer_store", "flat_store")): return "vmem_store"
     if op.startswith(("scratch_",)): return "scratch"
     if op == "s_waitcnt": return "s_waitcnt"
-    if op.startswith("s_memtime"): return "STAMP"
     if op.startswith(("s_cbranch", "s_branch")): return "branch"
     if op.startswith("s_barrier"): return "barrier"
     if op.startswith("s_nop"): return "s_nop"
@@ -61,9 +54,6 @@ for l in lines[i0 + 1:i1 + 1]:
         continue
     op = t.split()[0]
     k = klass(op)
-    if k == "STAMP":
-        blocks.append((name, cur)); cur, name = collections.Counter(), name + "+stamp"
-        continue
     cur[k] += 1
 blocks.append((name, cur))
 VALU = [k for k in ("valu_fma", "valu_addsub", "valu_mul", "valu_packed", "valu_trans", "valu_select", "valu_mov", "valu_cmp", "valu_lane", "valu_int_other")]
