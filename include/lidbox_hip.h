@@ -477,6 +477,24 @@ int lidbox_signal_rms(const float* signals, const int64_t* starts, const int64_t
 int lidbox_snr_mixer(const float* clean, const float* noise, const float* snr_db, int B, long N,
                      float* clean_norm, float* noise_new, float* noisy, lidbox_stream_t stream);
 
+/* features/audio.py:37-47 scipy_resample = scipy.signal.resample(x, M) (Fourier method, window=None) on a ragged batch:
+ * utterance b goes from in_lengths[b] = N to out_lengths[b] = M samples, read at signals[in_starts[b]..], written at
+ * out[out_starts[b]..].  Two chirp-z transforms of power-of-two length per utterance, fp32 throughout; the launches
+ * grow with the number of distinct transform sizes in the batch, not with B.  N, M <= 2^21; N = 0 needs M = 0; M = 0
+ * writes nothing.  The lengths come twice: as HOST arrays for planning and (with the starts) as DEVICE arrays for the
+ * kernels.  workspace: >= lidbox_resample_workspace() bytes, 16-byte aligned, no initialisation; 0 bytes when there is
+ * nothing to do, and also for lengths outside the supported range (lidbox_resample then reports the limit). */
+size_t lidbox_resample_workspace(const int64_t* in_lengths_host, const int64_t* out_lengths_host, int B);
+int lidbox_resample(const float* signals, const int64_t* in_starts, const int64_t* in_lengths, float* out,
+                    const int64_t* out_starts, const int64_t* out_lengths, const int64_t* in_lengths_host,
+                    const int64_t* out_lengths_host, int B, void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+/* features/audio.py:64-72 scipy_lfilter = scipy.signal.lfilter(f, 1.0, x) with zero initial state, per utterance:
+ * out[starts[b] + n] = sum_{k < K} coefs[b*K + k] * x[n - k] (x[< 0] = 0), the input's layout, K = num_coefs in 1 .. 4096
+ * (coefs [B, K] in device memory).  Summed in the fixed order k = 0 .. K-1: bit-identical whatever the batch.
+ * max_length: the longest utterance (host). */
+int lidbox_fir_filter(const float* signals, const int64_t* starts, const int64_t* lengths, int B, long max_length,
+                      const float* coefs, int num_coefs, float* out, lidbox_stream_t stream);
+
 /* lidbox/util.py:41-57 merge_chunk_predictions with the default stack_and_average: x [rows, D] sorted so that
  * the rows of segment s are segment_offsets[s] .. segment_offsets[s+1] (int64, device); out [num_segments, D]. */
 int lidbox_segment_mean(const float* x, const int64_t* segment_offsets, int num_segments, int D, float* out,

@@ -136,6 +136,9 @@ _SIGS = {
     "lidbox_peak_normalize_max": (_i, [_vp, _vp, _vp, _i, _f, _l, _i, _vp, _vp]),
     "lidbox_signal_rms": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "lidbox_snr_mixer": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp, _vp, _vp]),
+    "lidbox_resample_workspace": (_sz, [_vp, _vp, _i]),
+    "lidbox_resample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "lidbox_fir_filter": (_i, [_vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp]),
     "lidbox_freq_attention_fwd": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
     "lidbox_freq_attention_bwd": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp]),
     "lidbox_log_softmax_fwd": (_i, [_vp, _i, _i, _vp, _vp]),

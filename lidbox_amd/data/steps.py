@@ -6,6 +6,8 @@ dicts (the reference maps the same functions over a tf.data.Dataset); results ar
   compute_rms_vad       reference steps.py:417-432   energy VAD decisions             
   apply_vad             reference steps.py:183-200   drop the non-speech frames        
   create_signal_chunks  reference steps.py:579-632   fixed-length chunks, new ids      
+  random_signal_speed_change   reference steps.py:331-352   Fourier resampling at a random speed ratio
+  random_signal_fir_filtering  reference steps.py:355-368   random N(0, 1) FIR filter per signal
   extract_embeddings    reference steps.py:674-705   batched embedding extraction      
 
 The signal steps gather `launch_batch` elements into one ragged device batch per kernel launch
@@ -212,6 +214,69 @@ def create_signal_chunks(ds, length_ms, step_ms, max_pad_ms=0, deterministic_out
                 if "duration" in x:
                     out["duration"] = float(np.float32(ch.shape[1] / int(x["sample_rate"])))          # steps.py:597
                 yield out
+
+
+# ------------------------------------------------------------------ augmentation (csrc/augment.hip)
+def _selected(batch, flag):
+    """indexes of the elements a step processes: all, or those whose x[flag] is truthy (reference `if flag and not x[flag]`)"""
+    return [i for i, x in enumerate(batch) if not (flag and not x[flag])]
+
+
+def speed_change_rate(rng, sample_rate, min, max):
+    """one draw of steps.py:343-345 in float32: ratio = min + (max - min) * u, u = rng.random(float32);
+    in_rate = int32(ratio * float32(sample_rate)) truncated as tf.cast does"""
+    u = rng.random(dtype=np.float32)
+    ratio = np.float32(min) + (np.float32(max) - np.float32(min)) * u
+    return int(np.float32(ratio) * np.float32(sample_rate))
+
+
+def _augmented(batch, idx, signals):
+    out = list(batch)
+    for i, s in zip(idx, signals):
+        out[i] = dict(batch[i], signal=s)
+    return out
+
+
+def random_signal_speed_change(ds, min, max, flag=None, seed=None, launch_batch=256):
+    """reference steps.py:331-352: every selected signal is resampled (scipy.signal.resample semantics) from
+    (N * sample_rate) // in_rate samples, in_rate = sample_rate times a ratio drawn uniformly from [min, max]
+    (`speed_change_rate`; one np.random.default_rng(seed) per call, one draw per selected element in element order,
+    so the output does not depend on launch_batch).  The output length is exact where the reference's int32 product
+    wraps (signal_ops.resample_length)."""
+    logger.info("Applying random resampling to signals with a random speed ratio chosen uniformly at random from [%.3f, %.3f]",
+                min, max)
+    rng = np.random.default_rng(seed)
+    for batch in _launch_batches(ds, launch_batch):
+        idx = _selected(batch, flag)
+        if not idx:
+            yield from batch
+            continue
+        r = signal_ops.RaggedSignals.from_list([batch[i]["signal"] for i in idx])
+        m = []
+        for i, n in zip(idx, r.lengths_host):
+            sr = int(batch[i]["sample_rate"])
+            in_rate = speed_change_rate(rng, sr, min, max)
+            if in_rate <= 0:
+                raise ValueError("element %r: speed ratio gives an input rate of %d" % (batch[i].get("id"), in_rate))
+            m.append(signal_ops.resample_length(n, in_rate, sr))
+        yield from _augmented(batch, idx, signal_ops.resample(r, m).split())
+
+
+def random_signal_fir_filtering(ds, num_coefs=10, flag=None, seed=None, launch_batch=256):
+    """reference steps.py:355-368: every selected signal goes through lfilter(f, 1.0, signal) with num_coefs coefficients
+    drawn as np.random.default_rng(seed).standard_normal(num_coefs, dtype=np.float32), one draw per selected element in
+    element order (independent of launch_batch)."""
+    logger.info("Applying random FIR filters of size %d on signals", num_coefs)
+    rng = np.random.default_rng(seed)
+    num_coefs = int(num_coefs)
+    for batch in _launch_batches(ds, launch_batch):
+        idx = _selected(batch, flag)
+        if not idx:
+            yield from batch
+            continue
+        coefs = np.stack([rng.standard_normal(num_coefs, dtype=np.float32) for _ in idx])
+        r = signal_ops.RaggedSignals.from_list([batch[i]["signal"] for i in idx])
+        yield from _augmented(batch, idx, signal_ops.fir_filter(r, torch.from_numpy(coefs)).split())
 
 
 # ------------------------------------------------------------------ embeddings (SURVEY 8f.2)

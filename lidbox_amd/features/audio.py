@@ -4,12 +4,15 @@ names and defaults as the reference (cited per function, file:line relative to t
 checkout), over torch tensors on the HIP device.  All arithmetic runs in liblidbox_hip.so.
 The energy VAD, silence removal, peak normalisation, RMS and SNR-mixer helpers run on the
 ragged-batch kernels of csrc/signal.hip through `signal_ops`; 16-bit PCM is scaled and channel-averaged on the device
-(`pcm16_to_float`, `read_wav`: the RIFF header is parsed on the host, the samples cross PCIe as int16); MP3 decoding,
-resampling, WebRTC VAD and the random FIR augmentation stay out of scope (host libraries).
+(`pcm16_to_float`, `read_wav`: the RIFF header is parsed on the host, the samples cross PCIe as int16).  Fourier
+resampling (`scipy_resample`, `pyfunc_resample`) and FIR filtering (`scipy_lfilter`, `random_gaussian_fir_filter`) run on
+the ragged-batch kernels of csrc/augment.hip; the random FIR coefficients are drawn on the host with numpy.  MP3 decoding
+and WebRTC VAD stay out of scope (host libraries).
 """
 import math
 import threading
 
+import numpy as np
 import torch
 
 from .. import _native as nv
@@ -347,3 +350,30 @@ def remove_silence(signal, rate, window_ms=10, min_non_speech_ms=300):
 def snr_mixer(clean, noise, snr):
     """reference lidbox/features/audio.py:128-148 (rank-1 signals; `signal_ops.snr_mixer` takes batches)"""
     return signal_ops.snr_mixer(clean, noise, snr)
+
+
+# ------------------------------------------------------------------ augmentation (csrc/augment.hip)
+def scipy_resample(signal, in_rate, out_rate):
+    """reference lidbox/features/audio.py:37-39: scipy.signal.resample to (N * out_rate) // in_rate samples (the length is
+    exact; see signal_ops.resample_length for where the reference's int32 product differs)"""
+    r = _one(signal)
+    m = signal_ops.resample_length(r.lengths_host[0], _scalar(in_rate), _scalar(out_rate))
+    return signal_ops.resample(r, [m]).split()[0]
+
+
+def pyfunc_resample(signal, in_rate, out_rate):
+    """reference lidbox/features/audio.py:41-47 -> (resampled signal, out_rate)"""
+    return scipy_resample(signal, in_rate, out_rate), out_rate
+
+
+def scipy_lfilter(s, f):
+    """reference lidbox/features/audio.py:64-65: scipy.signal.lfilter(f, 1.0, s) with zero initial state"""
+    f = torch.as_tensor(f, dtype=torch.float32).reshape(1, -1)
+    return signal_ops.fir_filter(_one(s), f).split()[0]
+
+
+def random_gaussian_fir_filter(signal, num_coefs, seed=None):
+    """reference lidbox/features/audio.py:67-72: lfilter with num_coefs N(0, 1) coefficients, drawn on the host by
+    np.random.default_rng(seed).standard_normal(num_coefs, dtype=np.float32)"""
+    fir = np.random.default_rng(seed).standard_normal(int(_scalar(num_coefs)), dtype=np.float32)
+    return scipy_lfilter(signal, fir)

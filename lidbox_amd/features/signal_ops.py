@@ -1,6 +1,7 @@
 """
 Ragged-batch driver for the signal kernels of csrc/signal.hip: energy VAD, VAD application,
-fixed-length chunking, peak normalisation, RMS and the SNR mixer for MANY variable-length signals per launch.
+fixed-length chunking, peak normalisation, RMS and the SNR mixer for MANY variable-length signals per launch;
+and of csrc/augment.hip: Fourier resampling (speed change) and per-utterance FIR filtering.
 `lidbox_amd.features.audio` (single-signal functions with the reference's names) and
 `lidbox_amd.data.steps` (dataset steps) are thin layers over this module.
 
@@ -213,3 +214,55 @@ def snr_mixer(clean, noise, snr):
             nv.check(nv.lib.lidbox_snr_mixer(nv.ptr(c2), nv.ptr(z2), nv.ptr(s), B, N, nv.ptr(outs[0]), nv.ptr(outs[1]),
                                              nv.ptr(outs[2]), nv.current_stream()))
     return tuple(o.reshape(-1) if single else o for o in outs)
+
+
+MAX_RESAMPLE_LENGTH = 1 << 21    # samples in and out of lidbox_resample (131 s at 16 kHz)
+
+
+def resample_length(num_samples, in_rate, out_rate):
+    """output length of audio.py:37-39 computed exactly: (N * out_rate) // in_rate.  The reference evaluates
+    len * out_rate in the int32 of its numpy rate arguments, which wraps to a negative length once
+    N * out_rate >= 2^31 (beyond about 8.4 s at 16 kHz); here the product is a Python integer (deliberate divergence)."""
+    n, i, o = int(num_samples), int(in_rate), int(out_rate)
+    if i <= 0 or o <= 0:
+        raise ValueError("sample rates must be positive, got in_rate=%d out_rate=%d" % (i, o))
+    return (n * o) // i
+
+def resample(r, num_out):
+    """audio.py:37-40 (scipy.signal.resample) for every utterance: utterance b -> num_out[b] samples.
+    -> new RaggedSignals with 16-byte aligned starts"""
+    dev = r.flat.device
+    m = np.asarray(num_out, np.int64).reshape(-1)
+    if len(m) != r.B:
+        raise ValueError("num_out must have one entry per utterance")
+    starts, total = _aligned_starts(np.maximum(m, 0))
+    out = torch.zeros(max(total, ALIGN), dtype=torch.float32, device=dev)
+    n_h = np.ascontiguousarray(r.lengths_host)
+    m_h = np.ascontiguousarray(m)
+    with torch.cuda.device(dev):
+        wbytes = nv.lib.lidbox_resample_workspace(n_h.ctypes.data, m_h.ctypes.data, r.B)
+        ws = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+        starts_d = torch.from_numpy(starts).to(dev)
+        m_d = torch.from_numpy(m_h).to(dev)
+        nv.check(nv.lib.lidbox_resample(nv.ptr(r.flat), nv.ptr(r.starts), nv.ptr(r.lengths), nv.ptr(out), nv.ptr(starts_d),
+                                        nv.ptr(m_d), n_h.ctypes.data, m_h.ctypes.data, r.B, nv.ptr(ws), wbytes,
+                                        nv.current_stream()))
+    return RaggedSignals(out, starts, m)
+
+
+def fir_filter(r, coefs):
+    """audio.py:64-65 (scipy.signal.lfilter(f, 1.0, x)) for every utterance with its own row of coefs [B, K]
+    -> RaggedSignals with the input's layout (alignment gaps are left unspecified)"""
+    dev = r.flat.device
+    f = torch.as_tensor(coefs, dtype=torch.float32)
+    if f.dim() == 1:
+        f = f.reshape(1, -1).expand(r.B, -1)
+    if f.dim() != 2 or f.shape[0] != r.B:
+        raise ValueError("coefs must be [B, K] (or [K] shared by every utterance)")
+    f = f.to(dev).contiguous()
+    out = torch.empty_like(r.flat)
+    with torch.cuda.device(dev):
+        max_len = int(r.lengths_host.max()) if r.B else 0
+        nv.check(nv.lib.lidbox_fir_filter(nv.ptr(r.flat), nv.ptr(r.starts), nv.ptr(r.lengths), r.B, max_len, nv.ptr(f),
+                                          int(f.shape[1]), nv.ptr(out), nv.current_stream()))
+    return RaggedSignals(out, r.starts_host, r.lengths_host)
