@@ -685,6 +685,39 @@ int lidbox_scale(float* x, long n, float alpha, lidbox_stream_t stream);
 /* fill n floats with value (stream-ordered) */
 int lidbox_fill(float* x, long n, float value, lidbox_stream_t stream);
 
+/* ------------------------------------------------------------------ LSTM recurrence (lidbox/models/lstm.py:16, ap_lstm.py:32-35)
+ * tf.keras.layers.LSTM with the TF2 defaults (tanh, sigmoid recurrent activation, use_bias, zero initial state, no dropout, no
+ * masking), one or both directions of a Bidirectional(merge_mode="concat") layer in one call (dirs = 1 or 2; U1 is the reverse
+ * direction's recurrent kernel, which walks t from T-1 to 0 and writes its outputs at their original time index).  Gate order
+ * i, f, c, o; recurrent_kernel U_d [H, 4H] (Keras layout).  The input projection and every weight gradient are the caller's
+ * GEMMs (lidbox_gemm_nn / _tn / _nt); these calls are only the walk through time.
+ *   zg    [dirs][B][T][4H]: on entry to _fwd  X W_d + b_d; on return the gate activations (i, f, tanh z_c, o) backward needs;
+ *         _bwd overwrites them with dZ (the gradient of the pre-activations), so one forward feeds one backward
+ *   hseq  [B][T+2][dirs*H]: h_t of direction d at row t+1, columns d*H..d*H+H-1; the caller zeroes rows 0 and T+1 once and
+ *         they stay zero, so H_prev of the forward direction is rows 0..T-1 and of the reverse one rows 2..T+1
+ *   cseq  [dirs][B][T][H]: cell states
+ *   dh_seq (may be NULL) [B][T][dirs*H] with dh_batch_stride floats between utterances: the gradient of the output sequence;
+ *   dh_last (may be NULL) [B][dirs*H]: the gradient of each direction's final h (t = T-1 forward, t = 0 reverse).
+ * Two forms, chosen by H: resident (lidbox_lstm_resident_ok(H): H <= 80, U held in LDS for the whole launch -- 16 H^2 bytes
+ * fp32, 100 KiB at H = 80, plus backward's 40 KiB dZ tiles inside the 160 KiB of a CU -- one launch per pass, a row's results
+ * bit-identical whatever B and its position in the batch) and stepped (any H: one GEMM per step and direction plus one cell
+ * kernel, workspace lidbox_lstm_workspace bytes; 0 for the resident form).  Sums run in a fixed order, no atomics, no
+ * communication between workgroups.  B = 0 is a no-op. */
+int    lidbox_lstm_resident_ok(int H);
+size_t lidbox_lstm_workspace(int B, int T, int H, int dirs);
+int lidbox_lstm_fwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, float* hseq, float* cseq,
+                    void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+int lidbox_lstm_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* cseq,
+                    const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
+                    lidbox_stream_t stream);
+/* out[b, c] (ldo floats between rows) = alpha * mean_t x[b, t, c] (ap_lstm.py:37-41: Multiply by alpha, Concatenate, then
+ * GlobalAveragePooling1D -- each BLSTM pools into its half of the pooled vector); x rows through (batch_stride, row_stride).
+ * _bwd: dx[b, t, c] (=, or += when accumulate) alpha * dout[b, c] / T. */
+int lidbox_seq_avg_pool_fwd(const float* x, int B, int T, int C, long batch_stride, long row_stride, float alpha, float* out,
+                            long ldo, lidbox_stream_t stream);
+int lidbox_seq_avg_pool_bwd(const float* dout, long ldo, int B, int T, int C, float alpha, float* dx, long batch_stride,
+                            long row_stride, int accumulate, lidbox_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

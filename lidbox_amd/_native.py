@@ -185,6 +185,12 @@ _SIGS = {
     "lidbox_spatial_dropout": (_i, [_vp, _i, _i, _i, _l, _f, C.c_ulonglong, _vp, _vp, _vp]),
     "lidbox_copy_2d": (_i, [_vp, _sz, _vp, _sz, _sz, _sz, _vp]),
     "lidbox_zero_2d": (_i, [_vp, _sz, _sz, _sz, _vp]),
+    "lidbox_lstm_resident_ok": (_i, [_i]),
+    "lidbox_lstm_workspace": (_sz, [_i, _i, _i, _i]),
+    "lidbox_lstm_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "lidbox_lstm_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "lidbox_seq_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _f, _vp, _l, _vp]),
+    "lidbox_seq_avg_pool_bwd": (_i, [_vp, _l, _i, _i, _i, _f, _vp, _l, _l, _i, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():
