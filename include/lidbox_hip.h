@@ -639,6 +639,14 @@ int lidbox_bn_train_stats(const float* x, long R, int C, const float* gamma, con
                           float momentum, float* moving_mean, float* moving_var, float* mean_out, float* invstd_out,
                           float* scale_out, float* shift_out, void* workspace, size_t workspace_bytes,
                           lidbox_stream_t stream);
+/* lidbox_bn_train_stats with the moving-variance target chosen: bessel != 0 moves it towards the Bessel-corrected batch
+ * variance var * R / (R - 1) (what lidbox_bn_train_stats does: tf.keras' fused path, 4-D inputs), bessel == 0 towards the
+ * population variance (tf.keras' non-fused path, which 2-D inputs [B, C] take: bi_gru.py:35,38,41).  Normalisation is
+ * the same in both. */
+int lidbox_bn_train_stats_ex(const float* x, long R, int C, const float* gamma, const float* beta, float eps,
+                             float momentum, int bessel, float* moving_mean, float* moving_var, float* mean_out,
+                             float* invstd_out, float* scale_out, float* shift_out, void* workspace,
+                             size_t workspace_bytes, lidbox_stream_t stream);
 int lidbox_bn_infer_consts(const float* gamma, const float* beta, const float* moving_mean, const float* moving_var,
                            float eps, int C, float* scale_out, float* shift_out, lidbox_stream_t stream);
 int lidbox_bn_apply(const float* x, long R, int C, const float* scale, const float* shift, lidbox_rows_out_t y,
@@ -710,6 +718,30 @@ int lidbox_lstm_fwd(const float* U0, const float* U1, int dirs, int B, int T, in
 int lidbox_lstm_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* cseq,
                     const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
                     lidbox_stream_t stream);
+/* ------------------------------------------------------------------ GRU recurrence (lidbox/models/bi_gru.py:33-34)
+ * tf.keras.layers.GRU with the TF2 defaults (reset_after=True, tanh, sigmoid recurrent activation, use_bias, zero initial
+ * state, no dropout, no masking), one or both directions of a Bidirectional(merge_mode="concat") layer in one call (as the
+ * LSTM calls above: the reverse direction walks t from T-1 to 0 and writes at the original time index).  Gate order z, r, h;
+ * recurrent_kernel U_d [H, 3H], b_rec_d [3H] = row 1 of the Keras bias [2, 3H] (row 0, the input bias, belongs to the
+ * caller's projection).  Buffers:
+ *   zg    [dirs][B][T][3H]: on entry to _fwd X W_d + b_in_d; on return (z, r, hh); _bwd overwrites them with dZx = the
+ *         gradient of (x_z, x_r, x_h), so dW = X^T dZx, db_in = column sums of dZx, dX = dZx W^T
+ *   qh    [dirs][B][T][H]: _fwd writes q_h = (h_{t-1} U + b_rec)_h; _bwd overwrites it with dhh * r, the h block of dZrec =
+ *         (dZx_z, dZx_r, qh): dU = H_prev^T dZrec and db_rec = its column sums (two lidbox_gemm_tn calls with ldc = 3H)
+ *   hseq  [B][T+2][dirs*H]: as lidbox_lstm_fwd (rows 0 and T+1 zero, kept zero by the caller)
+ *   hlast (may be NULL) [B][dirs*H]: each direction's final h (t = T-1 forward, t = 0 reverse)
+ *   dh_seq / dh_last: as lidbox_lstm_bwd.  workspace: lidbox_gru_workspace bytes (backward's carried z * dh).
+ * One launch per time step for both directions: each workgroup owns 64 rows x 16 units, computes its slice of the
+ * recurrent product on fp32 MFMA and applies the cell in the same kernel.  Sums run in a fixed order, no atomics, no
+ * communication between workgroups: a row's results are bit-identical whatever B and its position in the batch.
+ * B = 0 is a no-op. */
+size_t lidbox_gru_workspace(int B, int T, int H, int dirs);
+int lidbox_gru_fwd(const float* U0, const float* U1, const float* b_rec0, const float* b_rec1, int dirs, int B, int T, int H,
+                   float* zg, float* hseq, float* qh, float* hlast, lidbox_stream_t stream);
+int lidbox_gru_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* hseq, float* qh,
+                   const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
+                   lidbox_stream_t stream);
+
 /* out[b, c] (ldo floats between rows) = alpha * mean_t x[b, t, c] (ap_lstm.py:37-41: Multiply by alpha, Concatenate, then
  * GlobalAveragePooling1D -- each BLSTM pools into its half of the pooled vector); x rows through (batch_stride, row_stride).
  * _bwd: dx[b, t, c] (=, or += when accumulate) alpha * dout[b, c] / T. */

@@ -178,6 +178,7 @@ _SIGS = {
     "lidbox_scale": (_i, [_vp, _l, _f, _vp]),
     "lidbox_bn_workspace": (_sz, [_l, _i]),
     "lidbox_bn_train_stats": (_i, [_vp, _l, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "lidbox_bn_train_stats_ex": (_i, [_vp, _l, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lidbox_bn_infer_consts": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "lidbox_bn_apply": (_i, [_vp, _l, _i, _vp, _vp, Rows, _vp]),
     "lidbox_bn_bwd": (_i, [_vp, Rows, _l, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -189,6 +190,9 @@ _SIGS = {
     "lidbox_lstm_workspace": (_sz, [_i, _i, _i, _i]),
     "lidbox_lstm_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lidbox_lstm_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "lidbox_gru_workspace": (_sz, [_i, _i, _i, _i]),
+    "lidbox_gru_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lidbox_gru_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
     "lidbox_seq_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _f, _vp, _l, _vp]),
     "lidbox_seq_avg_pool_bwd": (_i, [_vp, _l, _i, _i, _i, _f, _vp, _l, _l, _i, _vp]),
 }

@@ -8,7 +8,8 @@
 // (1 - momentum) towards them -- the running VARIANCE towards the Bessel-corrected batch variance var * n / (n - 1): the
 // layer's 4-D input with axis = -1 takes tf.keras' fused path, which keeps the fused kernel's unbiased estimate for the
 // running average (`_bessels_correction_test_only` is True by default) while normalising with the population variance;
-// inference uses the running statistics.
+// inference uses the running statistics.  lidbox_bn_train_stats_ex(bessel = 0) moves the running variance towards the
+// population variance instead: tf.keras' non-fused path, which 2-D inputs [B, C] take (bi_gru.py:35,38,41).
 //
 // All four kernels are HBM-bound streams over x (and dy): column sums are accumulated in FLOAT64 per thread (one pass gives
 // mean and E[x^2] without cancellation trouble), partials [slices][C] are combined in a fixed order (deterministic, no
@@ -98,7 +99,8 @@ __device__ __forceinline__ void bn_channel_sums(const double* __restrict__ parti
 // scale / shift of the apply kernel, and the moving-statistics update
 __global__ __launch_bounds__(256) void bn_stats_stage2(const double* __restrict__ partial, int slices, long R, int C,
                                 const float* __restrict__ gamma,
-                                const float* __restrict__ beta, float eps, float momentum, float* __restrict__ moving_mean,
+                                const float* __restrict__ beta, float eps, float momentum, int bessel,
+                                float* __restrict__ moving_mean,
                                 float* __restrict__ moving_var, float* __restrict__ mean_out, float* __restrict__ invstd_out,
                                 float* __restrict__ scale, float* __restrict__ shift) {
     const int c = blockIdx.x;
@@ -117,8 +119,8 @@ __global__ __launch_bounds__(256) void bn_stats_stage2(const double* __restrict_
     shift[c] = beta[c] - muf * sc;
     if (moving_mean) {
         moving_mean[c] = moving_mean[c] * momentum + muf * (1.f - momentum);
-        const float unbiased = R > 1 ? (float)(var * ((double)R / (double)(R - 1))) : varf;
-        moving_var[c] = moving_var[c] * momentum + unbiased * (1.f - momentum);
+        const float target = bessel && R > 1 ? (float)(var * ((double)R / (double)(R - 1))) : varf;
+        moving_var[c] = moving_var[c] * momentum + target * (1.f - momentum);
     }
 }
 
@@ -227,10 +229,10 @@ extern "C" size_t lidbox_bn_workspace(long R, int C) {
     return (size_t)bn_slices(R) * 2 * (size_t)C * sizeof(double) + 3 * (size_t)C * sizeof(float);
 }
 
-extern "C" int lidbox_bn_train_stats(const float* x, long R, int C, const float* gamma, const float* beta, float eps,
-                                     float momentum, float* moving_mean, float* moving_var, float* mean_out,
-                                     float* invstd_out, float* scale_out, float* shift_out, void* workspace,
-                                     size_t workspace_bytes, lidbox_stream_t stream) {
+extern "C" int lidbox_bn_train_stats_ex(const float* x, long R, int C, const float* gamma, const float* beta, float eps,
+                                        float momentum, int bessel, float* moving_mean, float* moving_var, float* mean_out,
+                                        float* invstd_out, float* scale_out, float* shift_out, void* workspace,
+                                        size_t workspace_bytes, lidbox_stream_t stream) {
     LBX_ARG(x && gamma && beta && mean_out && invstd_out && scale_out && shift_out, "pointers != NULL");
     LBX_ARG(R >= 1 && C >= 1, "R >= 1, C >= 1");
     LBX_ARG((moving_mean == nullptr) == (moving_var == nullptr), "moving_mean and moving_var come together");
@@ -246,9 +248,17 @@ extern "C" int lidbox_bn_train_stats(const float* x, long R, int C, const float*
                        (const float*)nullptr, none, R, C, rps, (const float*)nullptr, (const float*)nullptr, partial);
     LBX_LAUNCH_OK();
     hipLaunchKernelGGL(bn_stats_stage2, dim3((unsigned)C), dim3(256), 0, st, partial, slices, R, C, gamma, beta,
-                       eps, momentum, moving_mean, moving_var, mean_out, invstd_out, scale_out, shift_out);
+                       eps, momentum, bessel ? 1 : 0, moving_mean, moving_var, mean_out, invstd_out, scale_out, shift_out);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_train_stats(const float* x, long R, int C, const float* gamma, const float* beta, float eps,
+                                     float momentum, float* moving_mean, float* moving_var, float* mean_out,
+                                     float* invstd_out, float* scale_out, float* shift_out, void* workspace,
+                                     size_t workspace_bytes, lidbox_stream_t stream) {
+    return lidbox_bn_train_stats_ex(x, R, C, gamma, beta, eps, momentum, 1, moving_mean, moving_var, mean_out, invstd_out,
+                                    scale_out, shift_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lidbox_bn_infer_consts(const float* gamma, const float* beta, const float* moving_mean,
