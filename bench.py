@@ -2,7 +2,7 @@
 """
 bench.py -- utterances/s of the log-mel + x-vector train step on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,17 +24,24 @@ torch.distributed.run (N ranks on 127.0.0.1) and still prints exactly one line.
   3  configs[3]: MFCC(1:13) + CMVN -> lidbox.models.cnn classifier, 4 languages, bs 256, fp32
   4  configs[4], one GPU's shard: log-mel -> x-vector trunk -> segment1 -> L2 norm -> SparseAngularProximity + C_avg,
      100 languages, bs 512 per GPU, bf16 compute / fp32 master weights
-Every configuration prints the same one-line JSON (metric / value / roofline / cpu_baseline).
+Every configuration prints the same one-line JSON (metric / value / unit / ms_per_step / config ...).
 
-Extra measurements in the same process (rank 0):
+A plain run does only what that headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds, after the timed region and in the same process (the headline and the dumped arrays are the same either way):
+  sustained         the same captured steps replayed for >= --sustain-seconds more.
   step_events       median / min / p90 of per-step HIP-event times over K more graph-replayed steps (the headline value is
                     the wall-clock mean of the timed region).
+  grad_sync_exposed_wait_us   N > 1 (or a forced gradient exchange): what the compute stream waits for the all-reduce.
   roofline          fp32-MFMA roofline of the dominant GEMM kernel family: algorithmic flops of
                     its launches / HIP-event time of those launches, from an instrumented eager
-                    pass over the same steps (events cannot be placed inside a graph replay).
+                    pass over the same steps (events cannot be placed inside a graph replay).  Also `kernels`.
   roofline_feature  HBM roofline of the fused log-mel kernel (159 680 algorithmic bytes/utterance).
+  feature_api       config 1 only: throughput of the Python feature-extraction boundary next to the bare kernel.
+  secondary         default fp32 config 1 only: configs[3] fp32 and configs[4] bf16 shard, same timing protocol.
   cpu_baseline      oracle/torch_ref.py (the CPU restatement; TensorFlow cannot run here) timed on
                     the host cores on a bounded sample of the same workload -- N = 1 only.
+--no-cpu-baseline, --no-kernel-timing, --no-feature-api, --no-secondary, --sustain-seconds and --cpu-seconds shape these
+blocks and do nothing without --full.
 """
 import argparse
 import json
@@ -96,7 +103,7 @@ def parse_args():
                          "(0.35 for the cross-entropy configurations, 0 for config 4 whose angular loss does not collapse) holds the "
                          "loss well above 0.3 through the timed and sustained regions.  The work per step does not depend on it.")
     ap.add_argument("--sustain-seconds", type=float, default=6.0,
-                    help="after the timed region: replay the same captured steps for at least this long and report the rate as "
+                    help="--full, after the timed region: replay the same captured steps for at least this long and report the rate as "
                          "`sustained` (0 disables).  The timed region of the driver's --steps 20 is ~45 ms; this block is long enough "
                          "for a 5-second utilisation sampler to see the GPU busy and for clocks to settle")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -108,6 +115,11 @@ def parse_args():
     ap.add_argument("--compute-dtype", choices=["float32", "bfloat16"], default=None,
                     help="GEMM arithmetic; float32 is the BASELINE metric's configuration, bfloat16 = config 5's "
                          "bf16-compute / fp32-master variant of the same workload (default: what the configuration names)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: sustained, step_events, "
+                         "grad_sync_exposed_wait_us, roofline / kernels / roofline_feature, feature_api, secondary, cpu_baseline "
+                         "(see the module docstring).  Off by default: a plain run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
     a = ap.parse_args()
     if a.compute_dtype is None:
         a.compute_dtype = "bfloat16" if a.config == 4 else "float32"
@@ -835,9 +847,9 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = global_B * args.steps / elapsed
 
-    # the same replayed steps for >= --sustain-seconds (outside the timed region; max over ranks like the headline)
+    # --full: the same replayed steps for >= --sustain-seconds (outside the timed region; max over ranks like the headline)
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         def agree(dt):
             if world == 1:
                 return dt
@@ -853,18 +865,24 @@ def main():
                      "note": "the timed region's captured steps replayed for >= --sustain-seconds more (wall clock, barrier + "
                              "synchronize on both sides, max over ranks); `value` above is the K-step timed region"}
 
-    # per-step HIP events over K more steps (outside the timed region): the distribution behind the wall-clock mean
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for i, (e0, e1) in enumerate(evs):
-        j = args.warmup + args.steps + i + (sustained["steps"] if sustained else 0)   # continue the rotation of the timed loop
-        e0.record()
-        if not args.prefetch:
-            trainer.train_step(*batches[j % len(batches)])
-        else:
-            trainer.train_step(*batches[j % len(batches)], next_inputs=batches[(j + 1) % len(batches)][0])
-        e1.record()
-    torch.cuda.synchronize(dev)
-    step_ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+    # --full: per-step HIP events over K more steps (outside the timed region): the distribution behind the wall-clock mean
+    step_events = None
+    if args.full:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for i, (e0, e1) in enumerate(evs):
+            j = args.warmup + args.steps + i + (sustained["steps"] if sustained else 0)   # continue the rotation of the timed loop
+            e0.record()
+            if not args.prefetch:
+                trainer.train_step(*batches[j % len(batches)])
+            else:
+                trainer.train_step(*batches[j % len(batches)], next_inputs=batches[(j + 1) % len(batches)][0])
+            e1.record()
+        torch.cuda.synchronize(dev)
+        step_ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+        step_events = {"median_ms": round(step_ms[len(step_ms) // 2], 4), "min_ms": round(step_ms[0], 4),
+                       "p90_ms": round(step_ms[min(len(step_ms) - 1, (9 * len(step_ms)) // 10)], 4), "steps": len(step_ms),
+                       "note": "HIP events around each of K further graph-replayed steps (host launch gaps included); "
+                               "`value` / `ms_per_step` are the wall-clock mean of the timed region"}
 
     sync_active = trainer.sync.active
     result = {
@@ -872,10 +890,6 @@ def main():
         "value": round(value, 1), "unit": "utterances/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
-        "step_events": {"median_ms": round(step_ms[len(step_ms) // 2], 4), "min_ms": round(step_ms[0], 4),
-                        "p90_ms": round(step_ms[min(len(step_ms) - 1, (9 * len(step_ms)) // 10)], 4), "steps": len(step_ms),
-                        "note": "HIP events around each of K further graph-replayed steps (host launch gaps included); "
-                                "`value` / `ms_per_step` are the wall-clock mean of the timed region"},
         "config": {"workload": w["workload"], "baseline_config": args.config if world == 1 or args.config != 1 else 2,
                    "reference_model": w["model_name"],
                    "global_batch": global_B, "per_gpu_batch": B, "samples_per_utt": 32000, "frames": 198, "mel": 40,
@@ -896,6 +910,8 @@ def main():
                                 "language so that the timed backward passes carry real gradients (the work per step is the same "
                                 "either way)"},
     }
+    if step_events is not None:
+        result["step_events"] = step_events
     if sustained is not None:
         result["sustained"] = sustained
     if dumped is not None:
@@ -906,7 +922,8 @@ def main():
         bounds = trainer.sync.bounds
         per = trainer.sync.wire_bytes // max(1, trainer.sync.flat.numel())
         result["config"]["allreduce_bucket_bytes"] = [per * (b - a) for a, b in zip(bounds, bounds[1:])]
-        result["grad_sync_exposed_wait_us"] = exposed_wait(w, trainer, batches[0], dev, world)
+        if args.full:
+            result["grad_sync_exposed_wait_us"] = exposed_wait(w, trainer, batches[0], dev, world)
 
     sys.stdout.flush()
     # RCCL writes its banner through C stdio, which is fully buffered when stdout is not a terminal: flush the C
@@ -914,25 +931,25 @@ def main():
     import ctypes
     ctypes.CDLL(None).fflush(None)
     if rank == 0:
-        if not args.no_kernel_timing and world == 1:
+        if args.full and not args.no_kernel_timing and world == 1:
             nsteps = min(args.steps, 10)
             result["roofline"], result["kernels"], feat = kernel_pass(nv, w, trainer, batches[0], nsteps)
             if feat:
                 result["roofline_feature"] = feat
-        if world == 1 and args.config == 1 and not args.no_feature_api:
+        if args.full and world == 1 and args.config == 1 and not args.no_feature_api:
             result["feature_api"] = feature_api(nv, dev, B)
         # whole-step view of the same roofline: algorithmic train flops / step time
         result["step_tflops"] = round(value / world * w["flops_per_utt"] / 1e12, 2)
         if metric is not None:
             result["config"]["c_avg"] = round(float(metric.result()), 4)
-        # the other single-GPU configurations of BASELINE.json in the same process (default invocation only): configs[3]
+        # the other single-GPU configurations of BASELINE.json in the same process (--full, default configuration only): configs[3]
         # in fp32 and one GPU's shard of configs[4] in bf16, same step count and timing protocol
-        if (world == 1 and args.config == 1 and not bf16 and not args.no_secondary and args.batch == PER_GPU_BATCH
+        if (args.full and world == 1 and args.config == 1 and not bf16 and not args.no_secondary and args.batch == PER_GPU_BATCH
                 and not os.environ.get("LIDBOX_FORCE_GRAD_SYNC")):
             del trainer
             torch.cuda.empty_cache()
             result["secondary"] = [secondary_run(nv, 3, "float32", 256, dev, args), secondary_run(nv, 4, "bfloat16", 512, dev, args)]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, batch=B, num_langs=num_langs, **w["cpu_cfg"])
     os.dup2(saved_stdout_fd, 1)
     os.close(saved_stdout_fd)

@@ -147,7 +147,7 @@ def test_rccl_backend_between_graph_segments_world1():
     env = dict(os.environ, LIDBOX_FORCE_GRAD_SYNC="1", HSA_ENABLE_IPC_MODE_LEGACY="0", LIDBOX_REQUIRE_INGRAPH_SYNC="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-           "--batch", "32", "--no-cpu-baseline", "--no-kernel-timing"]
+           "--batch", "32", "--full", "--no-cpu-baseline", "--no-kernel-timing"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -183,11 +183,32 @@ def test_segmented_sync_is_refused_when_in_graph_is_required():
     assert p.returncode != 0 and "LIDBOX_REQUIRE_INGRAPH_SYNC" in (p.stdout + p.stderr)
 
 
+def test_bench_plain_line_is_the_headline_only():
+    """`python bench.py` without --full: one JSON line with the headline and its configuration, and none of the blocks that
+    take runs or passes of their own"""
+    import json
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in r, key
+    for key in ("sustained", "step_events", "grad_sync_exposed_wait_us", "roofline", "roofline_feature", "kernels", "feature_api",
+                "secondary", "cpu_baseline"):
+        assert key not in r, key
+    assert r["unit"] == "utterances/s" and r["dtype"] == "f32" and r["higher_is_better"] is True and r["steps"] == 4
+    assert abs(r["value"] - 256 * 1e3 / r["ms_per_step"]) <= 1e-3 * r["value"]
+    assert np.isfinite(r["config"]["final_loss"]) and r["config"]["grad_sync"] == "none"
+
+
 def test_bench_line_contract_single_process():
-    """`python bench.py` (no launcher): one JSON line with the contract's keys, the roofline of the dominant GEMM
+    """`python bench.py --full` (no launcher): one JSON line with the contract's keys, the roofline of the dominant GEMM
     instantiation from live HIP events and the feature kernel's HBM roofline"""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--sustain-seconds", "1.0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--sustain-seconds", "1.0"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

@@ -25,7 +25,7 @@ for k in sorted(set(fetch) | set(write)):
               "hbm_bytes_per_launch": int((2.0 * f + w) * 1024)}
 json.dump({"source_hash": bench.source_hash(), "note": "hbm_bytes_per_launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024; FETCH_SIZE doubled per the gfx950 "
                    "calibration in MI355X_MICROARCH.md; averaged over all launches of the kernel in `python bench.py "
-                   "--steps 10 --warmup 3 --no-cpu-baseline`; source_hash = sha1 of csrc/*.hip, *.h and include/*.h the counters were taken "
+                   "--full --steps 10 --warmup 3 --no-cpu-baseline`; source_hash = sha1 of csrc/*.hip, *.h and include/*.h the counters were taken "
                    "from (bench.py quotes a summary only next to the same sources)", "kernels": out}, open(sys.argv[3], "w"), indent=1)
 for k, v in sorted(out.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"])[:14]:
     print("%-52s launches=%-5d %8.1f MB/launch" % (k[:52], v["launches"], v["hbm_bytes_per_launch"] / 1e6))
