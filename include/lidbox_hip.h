@@ -742,6 +742,47 @@ int lidbox_gru_bwd(const float* U0, const float* U1, int dirs, int B, int T, int
                    const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
                    lidbox_stream_t stream);
 
+/* ------------------------------------------------------------------ Conv2D / MaxPool2D (lidbox/models/crnn.py:36-41)
+ * tf.keras.layers.Conv2D(C_out, k, padding="same") with stride 1 and an odd k, on images stored time-major: x [B][T][F][C_in]
+ * (channels innermost; the reference's image is [B, F, T, C], height = frequency).  W is the Keras kernel [k][k][C_in][C_out]
+ * with its first index over frequency and its second over time:
+ *   y[b, t, f, co] = act(bias[co] + sum_{kh, kw, ci} x[b, t + kw - p, f + kh - p, ci] W[kh, kw, ci, co]),  p = (k - 1) / 2,
+ * x zero outside the image; act = ReLU when relu != 0; bias may be NULL.  C_out must be a multiple of 16.  An implicit GEMM on
+ * fp32 MFMA (no im2col copy); each output is one fixed-order sum, the same whatever B and the utterance's place in the batch.
+ *   _dgrad: dx [B][T][F][C_in] = the gradient of x for dy [B][T][F][C_out] (the gradient in front of the ReLU): the same
+ *           convolution with the kernel rotated by 180 degrees and C_in / C_out swapped (C_in a multiple of 16); workspace:
+ *           lidbox_conv2d_dgrad_workspace bytes (the rotated copy).
+ *   _wgrad: dW [k][k][C_in][C_out] = sum over pixels of x-window * dy, db [C_out] (may be NULL) = column sums of dy, both
+ *           overwritten.  Pixels are split into fixed partitions (a function of the shape), and a second launch sums the
+ *           partials in partition order: bit-identical from run to run.  workspace: lidbox_conv2d_wgrad_workspace bytes.
+ * Workspaces 16-byte aligned.  B = 0 is a no-op (wgrad: zeros). */
+int    lidbox_conv2d_fwd(const float* x, int B, int T, int F, int C_in, const float* W, int k, int C_out, const float* bias,
+                         int relu, float* y, lidbox_stream_t stream);
+size_t lidbox_conv2d_dgrad_workspace(int k, int C_in, int C_out);
+int    lidbox_conv2d_dgrad(const float* dy, int B, int T, int F, int C_in, int C_out, const float* W, int k, float* dx,
+                           void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+size_t lidbox_conv2d_wgrad_workspace(int B, int T, int F, int C_in, int C_out, int k);
+int    lidbox_conv2d_wgrad(const float* x, const float* dy, int B, int T, int F, int C_in, int C_out, int k, float* dW,
+                           float* db, void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+/* BatchNormalization apply + MaxPool2D(2) ("valid", stride 2) on x [B][T][F][C]: v = x * scale[c] + shift[c] (the constants of
+ * lidbox_bn_train_stats / lidbox_bn_infer_consts; normalised before the maximum, since gamma may be negative), y [B][T/2][F/2][C]
+ * = the maximum of each 2 x 2 window, argmax [B][T/2][F/2][C] = the winner's code 2 * dfreq + dtime.  Ties go to the first
+ * maximum in the reference image's scan order: lower frequency row first, then lower time column.  An odd last row or column
+ * is dropped.  _bwd: dx [B][T][F][C] = dy at each window's winner, zero elsewhere (dropped cells included). */
+int lidbox_bn_maxpool2d_fwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift, float* y,
+                            unsigned char* argmax, lidbox_stream_t stream);
+int lidbox_maxpool2d_bwd(const float* dy, const unsigned char* argmax, int B, int T, int F, int C, float* dx,
+                         lidbox_stream_t stream);
+/* kernel_regularizer=l2(lambda) (crnn.py:39) on `count` <= 16 tensors params[offsets[t] .. + sizes[t]): grads (may be NULL)
+ * += 2 lambdas[t] grad_scale params, and loss[0] (may be NULL) += sum_t lambdas[t] sum params^2.  A fixed grid writes the
+ * gradient and per-workgroup partial sums (workspace: lidbox_l2_penalty_workspace bytes, needed when loss != NULL), a
+ * one-thread launch adds them in order: fixed summation order.  grad_scale: 1 / world_size when the gradient is all-reduced
+ * by a sum afterwards. */
+size_t lidbox_l2_penalty_workspace(void);
+int lidbox_l2_penalty(const float* params, float* grads, int count, const long* offsets, const long* sizes,
+                      const float* lambdas, float grad_scale, float* loss, void* workspace, size_t workspace_bytes,
+                      lidbox_stream_t stream);
+
 /* out[b, c] (ldo floats between rows) = alpha * mean_t x[b, t, c] (ap_lstm.py:37-41: Multiply by alpha, Concatenate, then
  * GlobalAveragePooling1D -- each BLSTM pools into its half of the pooled vector); x rows through (batch_stride, row_stride).
  * _bwd: dx[b, t, c] (=, or += when accumulate) alpha * dout[b, c] / T. */

@@ -193,6 +193,15 @@ _SIGS = {
     "lidbox_gru_workspace": (_sz, [_i, _i, _i, _i]),
     "lidbox_gru_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lidbox_gru_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "lidbox_conv2d_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "lidbox_conv2d_dgrad_workspace": (_sz, [_i, _i, _i]),
+    "lidbox_conv2d_dgrad": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "lidbox_conv2d_wgrad_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "lidbox_conv2d_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "lidbox_bn_maxpool2d_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lidbox_maxpool2d_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "lidbox_l2_penalty_workspace": (_sz, []),
+    "lidbox_l2_penalty": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _sz, _vp]),
     "lidbox_seq_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _f, _vp, _l, _vp]),
     "lidbox_seq_avg_pool_bwd": (_i, [_vp, _l, _i, _i, _i, _f, _vp, _l, _l, _i, _vp]),
 }

@@ -1,0 +1,570 @@
+// conv2d.hip -- Keras Conv2D(padding="same", stride 1), BatchNormalization + MaxPool2D(2) and the kernels' L2 penalty, gfx950.
+//
+// Replaces (reference file:line): lidbox/models/crnn.py:36-41, one block of five:
+//     Conv2D(f, k, activation="relu", padding="same", kernel_regularizer=l2(weight_decay)) -> BatchNormalization()
+//     -> MaxPool2D(2)
+// The reference convolves an image [B, F, T, C] (height = frequency, width = time).  Here images are stored time-major,
+// [B, T, F, C] with channels innermost, so the model input [B, T, F] is already the first block's image and the last pool
+// output [B, T5, F5, C] is already the BLSTM's input [B, T5, F5 * C] in Keras' feature order.  The kernel keeps the Keras
+// layout W[kh][kw][C_in][C_out] with kh over frequency and kw over time:
+//     y[b, t, f, co] = relu(bias[co] + sum_{kh, kw, ci} x[b, t + kw - p, f + kh - p, ci] W[kh, kw, ci, co]),  p = (k - 1) / 2
+// with x zero outside the image (no halo in storage: the operand loaders test the bounds).
+//
+// Forward is an implicit GEMM on fp32 MFMA (v_mfma_f32_16x16x4_f32): rows are output pixels m = (b, t, f), the contraction
+// runs over kidx = (kh, kw, ci) in the Keras order, so the B operand is W viewed as [k*k*C_in, C_out]; no im2col copy
+// exists.  A workgroup (4 waves) owns 128 pixels x BN output channels (BN = 16, 32 or 64) and walks the contraction in
+// chunks of 16 through LDS, loading the next chunk into registers while the current one feeds the MFMAs.  Every output is
+// one k-chain in a fixed order that does not depend on the pixel's place in the batch: an utterance gives the same bits
+// alone or inside a batch.
+//
+// dgrad (stride 1, same padding) is the same convolution of dY with the kernel rotated by 180 degrees and C_in / C_out
+// swapped: a small launch writes that copy into the workspace and the forward kernel runs on it.
+//
+// wgrad: dW[kidx][co] = sum_m xshift[m][kidx] dY[m][co] is the same tile code with rows = kidx and the contraction over
+// pixels.  The pixels are split into P fixed partitions (P depends on the shape only); each workgroup writes its partial
+// tile to the workspace, workgroups of the first kidx tile also the partial column sums of dY (the bias gradient), and a
+// second launch sums the partials in a fixed order.  No atomics: bit-identical from run to run.
+//
+// BN-apply + MaxPool2D: one pass reads the conv output, applies the BatchNormalization scale / shift (gamma may be
+// negative, so normalisation comes first) and takes the 2 x 2 maximum ("valid": an odd last row / column is dropped).
+// Ties go to the FIRST maximum in the reference image's scan order -- lower frequency row first, then lower time column
+// (TF's MaxPoolGrad and torch.nn.functional.max_pool2d) -- and the winner's code 2 * dfreq + dtime is kept for backward,
+// which gathers: each input cell takes its window's gradient when it is the recorded winner, zero otherwise (and zero for
+// the dropped cells).
+#include <stdint.h>
+
+#include "common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int CV_BM = 128;            // tile rows: 4 waves x 32
+constexpr int CV_KC = 16;             // contraction elements per LDS chunk
+constexpr int CV_LDA = CV_BM + 16;    // 16 (mod 64) banks between the 4 k rows a wave reads at once
+template <int BN>
+constexpr int cv_ldb() { return BN == 16 ? 16 : BN + 16; }
+
+struct ConvGeom {
+    int B, T, F, Cin, Cout, ks, pad;
+    long M;          // B * T * F pixels
+    int K;           // ks * ks * Cin
+};
+
+// the contraction index kidx = (kh, kw, ci) -> (time offset, frequency offset, element offset from the pixel's own x row)
+struct KTap {
+    int dt, df;
+    long delta;
+    bool ok;
+};
+
+__device__ __forceinline__ KTap ktap(const ConvGeom& g, int kidx) {
+    KTap r;
+    r.ok = kidx < g.K;
+    const int kk = r.ok ? kidx : 0;
+    const int ci = kk % g.Cin, q = kk / g.Cin;
+    r.dt = q % g.ks - g.pad;            // kw: time
+    r.df = q / g.ks - g.pad;            // kh: frequency
+    r.delta = ((long)r.dt * g.F + r.df) * g.Cin + ci;
+    return r;
+}
+
+// acc[i][j] += As[0..16)[rows w*32 + 16 i ..] . Bs[0..16)[16 j ..] over one LDS chunk
+template <int BN>
+__device__ __forceinline__ void mma_lds_chunk(f32x4 (&acc)[2][BN / 16], const float* As, const float* Bs, int w, int lane) {
+    constexpr int LDB = cv_ldb<BN>();
+    const int c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int kq = 0; kq < CV_KC; kq += 4) {
+        const int k = kq + g;
+        float a[2], b[BN / 16];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = As[k * CV_LDA + w * 32 + 16 * i + c];
+#pragma unroll
+        for (int j = 0; j < BN / 16; ++j) b[j] = Bs[k * LDB + 16 * j + c];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < BN / 16; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- forward (and dgrad)
+// grid (ceil(M / 128), Cout / BN); thread (kk = tid & 15, r0 = tid >> 4) loads A[r0 + 16 j][kk], j < 8
+template <int BN>
+__global__ __launch_bounds__(256) void conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                       const float* __restrict__ bias, int relu, float* __restrict__ y,
+                                                       const ConvGeom g) {
+    constexpr int LDB = cv_ldb<BN>();
+    constexpr int BQ = CV_KC * BN / 256;      // B-operand loads per thread and chunk (1, 2 or 4)
+    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long m0 = (long)blockIdx.x * CV_BM;
+    const int n0 = blockIdx.y * BN;
+    const int kk = tid & 15, r0 = tid >> 4;
+    int tt[8], ff[8];
+    bool rok[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long m = m0 + r0 + 16 * j;
+        rok[j] = m < g.M;
+        const long mm = rok[j] ? m : 0;
+        ff[j] = (int)(mm % g.F);
+        tt[j] = (int)((mm / g.F) % g.T);
+    }
+    float av[8], bv[BQ];
+    auto load = [&](int kc) {
+        const KTap tp = ktap(g, kc + kk);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int t2 = tt[j] + tp.dt, f2 = ff[j] + tp.df;
+            const bool ok = rok[j] && tp.ok && (unsigned)t2 < (unsigned)g.T && (unsigned)f2 < (unsigned)g.F;
+            av[j] = ok ? x[(m0 + r0 + 16 * j) * g.Cin + tp.delta] : 0.0f;
+        }
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+            bv[q] = kc + kr < g.K ? W[(long)(kc + kr) * g.Cout + n0 + n] : 0.0f;
+        }
+    };
+    f32x4 acc[2][BN / 16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    load(0);
+    for (int kc = 0; kc < g.K; kc += CV_KC) {
+        __syncthreads();                                  // the previous chunk's LDS reads are done
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[kk * CV_LDA + r0 + 16 * j] = av[j];
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+            Bs[kr * LDB + n] = bv[q];
+        }
+        __syncthreads();
+        if (kc + CV_KC < g.K) load(kc + CV_KC);
+        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
+    }
+    // epilogue: lane (c, q) holds column 16 j + c of rows 16 i + 4 q + r (the 16x16 C/D map)
+    const int c = lane & 15, q4 = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < BN / 16; ++j) {
+        const int n = n0 + 16 * j + c;
+        const float bb = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long m = m0 + w * 32 + 16 * i + 4 * q4 + r;
+                if (m >= g.M) continue;
+                float v = acc[i][j][r] + bb;
+                if (relu) v = fmaxf(v, 0.0f);
+                y[m * g.Cout + n] = v;
+            }
+    }
+}
+
+// Wd[kh'][kw'][co][ci] = W[k-1-kh'][k-1-kw'][ci][co]: the kernel of the transposed convolution
+__global__ __launch_bounds__(256) void conv_rot_kernel(const float* __restrict__ W, float* __restrict__ Wd, int ks, int Cin,
+                                                       int Cout) {
+    const long n = (long)ks * ks * Cin * Cout;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int ci = (int)(i % Cin);
+        long q = i / Cin;
+        const int co = (int)(q % Cout);
+        q /= Cout;
+        const int kw = (int)(q % ks), kh = (int)(q / ks);
+        Wd[i] = W[(((long)(ks - 1 - kh) * ks + (ks - 1 - kw)) * Cin + ci) * Cout + co];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- wgrad
+// grid (ceil(K / 128), Cout / BN, P).  Partition p covers pixels [p * per, min(M, (p + 1) * per)).  Thread (kk = tid & 127,
+// p0 = tid >> 7) loads A[pixel p0 + 2 j][kidx kk], j < 8.
+template <int BN>
+__global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                         float* __restrict__ part, float* __restrict__ dbpart, long per,
+                                                         int P, const ConvGeom g) {
+    constexpr int LDB = cv_ldb<BN>();
+    constexpr int BQ = CV_KC * BN / 256;
+    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int k0 = blockIdx.x * CV_BM, n0 = blockIdx.y * BN, p = blockIdx.z;
+    const long mlo = (long)p * per, mhi = min(g.M, mlo + per);
+    const int kk = tid & 127, p0 = tid >> 7;
+    const KTap tp = ktap(g, k0 + kk);
+    const bool bias_tile = blockIdx.x == 0;
+    float av[8], bv[BQ];
+    auto load = [&](long mc) {
+        // (t, f) of pixel mc + p0, then stepped by 2 pixels
+        long m = mc + p0;
+        int f = (int)(m % g.F), t = (int)((m / g.F) % g.T);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int t2 = t + tp.dt, f2 = f + tp.df;
+            const bool ok = m < mhi && tp.ok && (unsigned)t2 < (unsigned)g.T && (unsigned)f2 < (unsigned)g.F;
+            av[j] = ok ? x[m * g.Cin + tp.delta] : 0.0f;
+            m += 2;
+            f += 2;
+            while (f >= g.F) {
+                f -= g.F;
+                if (++t == g.T) t = 0;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, pr = e / BN, n = e - pr * BN;
+            bv[q] = mc + pr < mhi ? dy[(mc + pr) * g.Cout + n0 + n] : 0.0f;
+        }
+    };
+    f32x4 acc[2][BN / 16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float dbacc = 0.0f;
+    if (mlo < mhi) load(mlo);
+    for (long mc = mlo; mc < mhi; mc += CV_KC) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[(p0 + 2 * j) * CV_LDA + kk] = av[j];
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, pr = e / BN, n = e - pr * BN;
+            Bs[pr * LDB + n] = bv[q];
+        }
+        __syncthreads();
+        if (mc + CV_KC < mhi) load(mc + CV_KC);
+        if (bias_tile && tid < BN) {
+#pragma unroll
+            for (int pr = 0; pr < CV_KC; ++pr) dbacc += Bs[pr * LDB + tid];
+        }
+        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
+    }
+    const int c = lane & 15, q4 = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < BN / 16; ++j) {
+        const int n = n0 + 16 * j + c;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int kr = k0 + w * 32 + 16 * i + 4 * q4 + r;
+                if (kr < g.K) part[((long)kr * g.Cout + n) * P + p] = acc[i][j][r];
+            }
+    }
+    if (bias_tile && tid < BN) dbpart[(long)(n0 + tid) * P + p] = dbacc;
+}
+
+// dW[i] = sum_p part[i][p] (i < K * Cout), db[co] = sum_p dbpart[co][p], in a fixed order.  Few partitions (P < 64): one
+// thread per output, p in order.  Many: one wave per output, lane l sums p = l, l + 64, ... in order, then a fixed xor tree.
+__device__ __forceinline__ const float* wgrad_src(const float* part, const float* dbpart, int P, long nw, long i) {
+    return i < nw ? part + i * P : dbpart + (i - nw) * P;
+}
+
+__device__ __forceinline__ float* wgrad_dst(float* dW, float* db, long nw, long i) { return i < nw ? dW + i : db + (i - nw); }
+
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ dbpart,
+                                                                int P, long nw, long n, float* __restrict__ dW,
+                                                                float* __restrict__ db) {
+    const long i = blockIdx.x * 256L + threadIdx.x;
+    if (i >= n) return;
+    const float* src = wgrad_src(part, dbpart, P, nw, i);
+    float s = 0.0f;
+    for (int p = 0; p < P; ++p) s += src[p];
+    *wgrad_dst(dW, db, nw, i) = s;
+}
+
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_wide_kernel(const float* __restrict__ part,
+                                                                     const float* __restrict__ dbpart, int P, long nw, long n,
+                                                                     float* __restrict__ dW, float* __restrict__ db) {
+    const long i = blockIdx.x * 4L + (threadIdx.x >> 6);
+    if (i >= n) return;                                       // whole waves leave together: wave_sum stays uniform
+    const int lane = threadIdx.x & 63;
+    const float* src = wgrad_src(part, dbpart, P, nw, i);
+    float s = 0.0f;
+    for (int p = lane; p < P; p += 64) s += src[p];
+    s = wave_sum(s);
+    if (lane == 0) *wgrad_dst(dW, db, nw, i) = s;
+}
+
+// ---------------------------------------------------------------------------------------------- BN-apply + MaxPool2D
+__global__ __launch_bounds__(256) void bn_maxpool_fwd_kernel(const float* __restrict__ x, int T, int F, int C,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             float* __restrict__ y, uint8_t* __restrict__ code, long n) {
+    const long i = blockIdx.x * 256L + threadIdx.x;
+    if (i >= n) return;
+    const int T2 = T / 2, F2 = F / 2;
+    const int c = (int)(i % C);
+    long q = i / C;
+    const int f2 = (int)(q % F2);
+    q /= F2;
+    const int t2 = (int)(q % T2);
+    const long b = q / T2;
+    const float* p = x + (((b * T + 2 * t2) * F) + 2 * f2) * C + c;
+    const float sc = scale[c], sh = shift[c];
+    // the reference image's scan order: (freq 0, time 0), (freq 0, time 1), (freq 1, time 0), (freq 1, time 1)
+    const long off[4] = {0, (long)F * C, C, (long)F * C + C};
+    float best = p[off[0]] * sc + sh;
+    int bc = 0;
+#pragma unroll
+    for (int e = 1; e < 4; ++e) {
+        const float v = p[off[e]] * sc + sh;
+        if (v > best) {
+            best = v;
+            bc = e;
+        }
+    }
+    y[i] = best;
+    code[i] = (uint8_t)bc;
+}
+
+__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ code, int T,
+                                                          int F, int C, float* __restrict__ dx, long n) {
+    const long i = blockIdx.x * 256L + threadIdx.x;
+    if (i >= n) return;
+    const int T2 = T / 2, F2 = F / 2;
+    const int c = (int)(i % C);
+    long q = i / C;
+    const int f = (int)(q % F);
+    q /= F;
+    const int t = (int)(q % T);
+    const long b = q / T;
+    float v = 0.0f;
+    if ((t >> 1) < T2 && (f >> 1) < F2) {
+        const long o = ((b * T2 + (t >> 1)) * F2 + (f >> 1)) * C + c;
+        if (code[o] == (uint8_t)(2 * (f & 1) + (t & 1))) v = dy[o];
+    }
+    dx[i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------- L2 penalty
+constexpr int L2_MAX = 16;
+constexpr int L2_BLOCKS = 128;
+
+struct L2Args {
+    const float* w[L2_MAX];
+    float* g[L2_MAX];
+    long n[L2_MAX];
+    float lam[L2_MAX];
+    int count;
+    float gscale;
+    float* partial;      // [L2_BLOCKS] (NULL: no loss)
+};
+
+// workgroup b owns the slice [b per, (b + 1) per) of the tensors laid end to end: g += 2 lam gscale w there, and
+// partial[b] = sum lam w^2 over it (per-thread strided sums, then a fixed tree)
+__global__ __launch_bounds__(256) void l2_penalty_kernel(const L2Args a, long per) {
+    __shared__ float red[4];
+    const long blo = blockIdx.x * per, bhi = blo + per;
+    float s = 0.0f;
+    long base = 0;
+    for (int t = 0; t < a.count; ++t) {
+        const long lo = max(blo, base), hi = min(bhi, base + a.n[t]);
+        const float* w = a.w[t] - base;
+        float* g = a.g[t] ? a.g[t] - base : nullptr;
+        const float lam = a.lam[t], k = 2.0f * lam * a.gscale;
+        float st = 0.0f;
+        for (long i = lo + threadIdx.x; i < hi; i += 256) {
+            const float v = w[i];
+            if (g) g[i] += k * v;
+            st += v * v;
+        }
+        s += lam * st;
+        base += a.n[t];
+    }
+    if (!a.partial) return;
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(64) void l2_loss_kernel(const float* __restrict__ partial, float* __restrict__ loss) {
+    if (threadIdx.x != 0) return;
+    float s = 0.0f;
+    for (int b = 0; b < L2_BLOCKS; ++b) s += partial[b];
+    loss[0] += s;
+}
+
+int conv_check(const char* fn, int B, int T, int F, int Cin, int Cout, int ks) {
+    // M = B * T * F < 2^31 keeps grid.x = ceil(M / 128) of the forward launch inside what a launch accepts
+    if (B < 0 || T < 1 || F < 1 || Cin < 1 || Cout < 16 || Cout % 16 != 0 || ks < 1 || ks % 2 == 0 ||
+        (long)B * T * F >= (1L << 31) || (long)B * T * F * (Cin > Cout ? Cin : Cout) >= (1L << 40) ||
+        (long)ks * ks * (Cin > Cout ? Cin : Cout) > (1 << 20)) {
+        lidbox_set_error("%s: invalid argument: B >= 0, T, F, C_in >= 1, C_out a multiple of 16, odd k, sizes in range", fn);
+        return LIDBOX_E_INVALID;
+    }
+    return LIDBOX_OK;
+}
+
+ConvGeom geom(int B, int T, int F, int Cin, int Cout, int ks) {
+    return ConvGeom{B, T, F, Cin, Cout, ks, (ks - 1) / 2, (long)B * T * F, ks * ks * Cin};
+}
+
+int conv_tile_n(int Cout) { return Cout % 64 == 0 ? 64 : Cout % 32 == 0 ? 32 : 16; }
+
+int launch_fwd(const float* x, const float* W, const float* bias, int relu, float* y, const ConvGeom& g, hipStream_t st) {
+    const int bn = conv_tile_n(g.Cout);
+    const dim3 grid((unsigned)lbx_cdiv(g.M, CV_BM), (unsigned)(g.Cout / bn));
+    if (bn == 64)
+        hipLaunchKernelGGL(conv_fwd_kernel<64>, grid, dim3(256), 0, st, x, W, bias, relu, y, g);
+    else if (bn == 32)
+        hipLaunchKernelGGL(conv_fwd_kernel<32>, grid, dim3(256), 0, st, x, W, bias, relu, y, g);
+    else
+        hipLaunchKernelGGL(conv_fwd_kernel<16>, grid, dim3(256), 0, st, x, W, bias, relu, y, g);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+// wgrad partitions: enough workgroups to cover the chip about four times, at least 512 pixels each, at most 1024 partitions
+void wgrad_plan(const ConvGeom& g, int* P, long* per) {
+    const long tiles = lbx_cdiv(g.K, CV_BM) * (g.Cout / conv_tile_n(g.Cout));
+    long p = lbx_cdiv(1024, tiles);
+    p = p < lbx_cdiv(g.M, 512) ? p : lbx_cdiv(g.M, 512);
+    p = p < 1024 ? p : 1024;
+    p = p > 1 ? p : 1;
+    const long chunks = lbx_cdiv(lbx_cdiv(g.M, CV_KC), p);
+    *per = chunks * CV_KC;
+    *P = (int)p;
+}
+
+}  // namespace
+
+extern "C" int lidbox_conv2d_fwd(const float* x, int B, int T, int F, int C_in, const float* W, int k, int C_out,
+                                 const float* bias, int relu, float* y, lidbox_stream_t stream) {
+    if (int e = conv_check(__func__, B, T, F, C_in, C_out, k)) return e;
+    LBX_ARG(x && W && y, "x, W, y != NULL");
+    if (B == 0) return LIDBOX_OK;
+    return launch_fwd(x, W, bias, relu ? 1 : 0, y, geom(B, T, F, C_in, C_out, k), (hipStream_t)stream);
+}
+
+extern "C" size_t lidbox_conv2d_dgrad_workspace(int k, int C_in, int C_out) {
+    if (k < 1 || C_in < 1 || C_out < 1) return 0;
+    return (size_t)k * k * C_in * C_out * sizeof(float);
+}
+
+extern "C" int lidbox_conv2d_dgrad(const float* dy, int B, int T, int F, int C_in, int C_out, const float* W, int k, float* dx,
+                                   void* workspace, size_t workspace_bytes, lidbox_stream_t stream) {
+    if (int e = conv_check(__func__, B, T, F, C_out, C_in, k)) return e;
+    LBX_ARG(dy && W && dx, "dy, W, dx != NULL");
+    if (B == 0) return LIDBOX_OK;
+    LBX_ARG(workspace && workspace_bytes >= lidbox_conv2d_dgrad_workspace(k, C_in, C_out) && ((uintptr_t)workspace & 15) == 0,
+            "workspace >= lidbox_conv2d_dgrad_workspace() bytes, 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* Wd = (float*)workspace;
+    const long nw = (long)k * k * C_in * C_out;
+    hipLaunchKernelGGL(conv_rot_kernel, dim3((unsigned)(lbx_cdiv(nw, 256) < 1024 ? lbx_cdiv(nw, 256) : 1024)), dim3(256), 0, st,
+                       W, Wd, k, C_in, C_out);
+    LBX_LAUNCH_OK();
+    return launch_fwd(dy, Wd, nullptr, 0, dx, geom(B, T, F, C_out, C_in, k), st);
+}
+
+extern "C" size_t lidbox_conv2d_wgrad_workspace(int B, int T, int F, int C_in, int C_out, int k) {
+    if (B < 1 || T < 1 || F < 1 || C_in < 1 || C_out < 16 || C_out % 16 != 0 || k < 1) return 0;
+    const ConvGeom g = geom(B, T, F, C_in, C_out, k);
+    int P;
+    long per;
+    wgrad_plan(g, &P, &per);
+    return (size_t)P * ((size_t)g.K * C_out + C_out) * sizeof(float);
+}
+
+extern "C" int lidbox_conv2d_wgrad(const float* x, const float* dy, int B, int T, int F, int C_in, int C_out, int k, float* dW,
+                                   float* db, void* workspace, size_t workspace_bytes, lidbox_stream_t stream) {
+    if (int e = conv_check(__func__, B, T, F, C_in, C_out, k)) return e;
+    LBX_ARG(x && dy && dW, "x, dy, dW != NULL");
+    hipStream_t st = (hipStream_t)stream;
+    const ConvGeom g = geom(B, T, F, C_in, C_out, k);
+    const long nw = (long)g.K * C_out;
+    if (B == 0) {
+        LBX_HIP(hipMemsetAsync(dW, 0, nw * sizeof(float), st));
+        if (db) LBX_HIP(hipMemsetAsync(db, 0, C_out * sizeof(float), st));
+        return LIDBOX_OK;
+    }
+    LBX_ARG(workspace && workspace_bytes >= lidbox_conv2d_wgrad_workspace(B, T, F, C_in, C_out, k) &&
+                ((uintptr_t)workspace & 15) == 0,
+            "workspace >= lidbox_conv2d_wgrad_workspace() bytes, 16-byte aligned");
+    int P;
+    long per;
+    wgrad_plan(g, &P, &per);
+    float* part = (float*)workspace;
+    float* dbpart = part + (long)P * nw;
+    const int bn = conv_tile_n(C_out);
+    const dim3 grid((unsigned)lbx_cdiv(g.K, CV_BM), (unsigned)(C_out / bn), (unsigned)P);
+    if (bn == 64)
+        hipLaunchKernelGGL(conv_wgrad_kernel<64>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+    else if (bn == 32)
+        hipLaunchKernelGGL(conv_wgrad_kernel<32>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+    else
+        hipLaunchKernelGGL(conv_wgrad_kernel<16>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+    LBX_LAUNCH_OK();
+    const long nout = nw + (db ? C_out : 0);
+    if (P >= 64)
+        hipLaunchKernelGGL(conv_wgrad_reduce_wide_kernel, dim3((unsigned)lbx_cdiv(nout, 4)), dim3(256), 0, st, part, dbpart, P, nw,
+                           nout, dW, db);
+    else
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)lbx_cdiv(nout, 256)), dim3(256), 0, st, part, dbpart, P, nw, nout,
+                           dW, db);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_maxpool2d_fwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift,
+                                       float* y, unsigned char* argmax, lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && T >= 2 && F >= 2 && C >= 1 && (long)B * T * F * C < (1L << 40), "B >= 0, T >= 2, F >= 2, C >= 1");
+    LBX_ARG(x && scale && shift && y && argmax, "pointers != NULL");
+    const long n = (long)B * (T / 2) * (F / 2) * C;
+    if (n == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(bn_maxpool_fwd_kernel, dim3((unsigned)lbx_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, T, F, C,
+                       scale, shift, y, argmax, n);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_maxpool2d_bwd(const float* dy, const unsigned char* argmax, int B, int T, int F, int C, float* dx,
+                                    lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && T >= 2 && F >= 2 && C >= 1 && (long)B * T * F * C < (1L << 40), "B >= 0, T >= 2, F >= 2, C >= 1");
+    LBX_ARG(dy && argmax && dx, "pointers != NULL");
+    const long n = (long)B * T * F * C;
+    if (n == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)lbx_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, dy, argmax, T, F,
+                       C, dx, n);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" size_t lidbox_l2_penalty_workspace(void) { return L2_BLOCKS * sizeof(float); }
+
+extern "C" int lidbox_l2_penalty(const float* params, float* grads, int count, const long* offsets, const long* sizes,
+                                 const float* lambdas, float grad_scale, float* loss, void* workspace, size_t workspace_bytes,
+                                 lidbox_stream_t stream) {
+    LBX_ARG(params && count >= 0 && count <= L2_MAX && (count == 0 || (offsets && sizes && lambdas)),
+            "params != NULL, 0 <= count <= 16, offsets / sizes / lambdas != NULL");
+    LBX_ARG(!loss || (workspace && workspace_bytes >= lidbox_l2_penalty_workspace() && ((uintptr_t)workspace & 3) == 0),
+            "workspace >= lidbox_l2_penalty_workspace() bytes when loss != NULL");
+    if (count == 0 || (!grads && !loss)) return LIDBOX_OK;
+    L2Args a{};
+    long total = 0;
+    for (int t = 0; t < count; ++t) {
+        LBX_ARG(offsets[t] >= 0 && sizes[t] >= 0, "offsets, sizes >= 0");
+        a.w[t] = params + offsets[t];
+        a.g[t] = grads ? grads + offsets[t] : nullptr;
+        a.n[t] = sizes[t];
+        a.lam[t] = lambdas[t];
+        total += sizes[t];
+    }
+    a.count = count;
+    a.gscale = grad_scale;
+    a.partial = loss ? (float*)workspace : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(l2_penalty_kernel, dim3(L2_BLOCKS), dim3(256), 0, st, a, lbx_cdiv(total, L2_BLOCKS));
+    LBX_LAUNCH_OK();
+    if (loss) {
+        hipLaunchKernelGGL(l2_loss_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, loss);
+        LBX_LAUNCH_OK();
+    }
+    return LIDBOX_OK;
+}

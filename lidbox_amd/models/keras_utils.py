@@ -405,6 +405,8 @@ class KerasWrapper:
                 else:
                     m.update_state(ys, scores)
         logs = {"loss": total / max(1, count)}
+        if getattr(self.keras_model, "regularizers", None):
+            logs["loss"] += self.keras_model.regularization_loss()          # Keras' evaluate adds the kernel penalties too
         for m in self.metrics:
             logs[getattr(m, "name", type(m).__name__)] = float(m.result())
         return logs

@@ -249,6 +249,11 @@ class Trainer:
         self.split_conv = self.splits[-1] if self.splits else None
         # grad_wire_dtype: "bfloat16" halves the bytes of the gradient exchange (GradSync); default: the fp32 buffer in place
         self.sync = GradSync(model.flat_grad, bounds, group, wire_dtype=grad_wire_dtype)
+        # kernel regularisers (model.regularizers: [(parameter, lambda)], crnn.py:39): applied behind the backward pass that
+        # completes their gradients, before any exchange; a model without them gets no launch
+        self.regularized = bool(getattr(model, "regularizers", None))
+        if self.regularized and len(self.splits) > 0:
+            raise ValueError("kernel regularisers need the single-bucket gradient exchange (num_buckets=1)")
         # overlap_wgrad: run wgrad GEMMs on a second stream concurrently with the dgrad chain.  Measured neutral
         # (96.1k vs 97.1k utt/s at bs 256): both are bound by the same matrix pipes.  Off by default.
         # fuse_output: the last Dense, log_softmax, the cross-entropy and their backward as two small launches when the model allows
@@ -469,6 +474,8 @@ class Trainer:
         lo_edges = self.splits[::-1] + [0]
         if k == 0:
             self.model.backward_head_ws(ws)
+            if self.regularized:
+                self._apply_regularizers(ws)
         for i in range(hi_edges[k] - 1, lo_edges[k] - 1, -1):
             self.model.backward_conv_ws(ws, i)
         self._prepared = False
@@ -481,6 +488,12 @@ class Trainer:
             self._prepared = True
         self.model.flush_reduce_jobs(ws)       # carried wgrad reduces still open: the stage's gradient bucket must be final
         self.model.join_wgrad()
+
+    def _apply_regularizers(self, ws):
+        """loss += lambda sum W^2 and flat_grad += 2 lambda W for every regularised kernel (Keras adds the terms to the loss it
+        differentiates).  Under data parallelism the all-reduce SUMS the ranks' gradients, so each rank adds 1/world of
+        the penalty gradient and the optimizer sees it once."""
+        self.model.apply_regularizers(self.model.flat_grad, ws.loss, 1.0 / self.sync.world)
 
     @property
     def num_stages(self):
@@ -729,6 +742,8 @@ class Trainer:
             finally:
                 self._warming = was
             self.model.backward_ws(ws)
+            if self.regularized:
+                self._apply_regularizers(ws)
             return ws.loss[0], self.model.flat_grad
 
     @property
