@@ -679,6 +679,13 @@ int lidbox_dropout_rows(lidbox_rows_out_t x, int C, float rate, unsigned long lo
 int lidbox_spatial_dropout(float* x, int B, int T, int C, long batch_stride, float rate,
                            unsigned long long seed, const void* step_counter, float* mask_out,
                            lidbox_stream_t stream);
+/* GaussianNoise(stddev) -> Dropout(rate, noise_shape=(None, 1, C)) of clstm.py:48-49 in one pass, in place on x [B, T, C]
+ * (row stride C, batch_stride floats between utterances): x = (x + stddev * n) * mask, n a standard normal drawn from
+ * (seed, *step_counter, b, t, c) (Box-Muller over two counter-based uniforms), mask the draw of lidbox_spatial_dropout for
+ * the same (seed, *step_counter, b, c).  stddev = 0 gives lidbox_spatial_dropout's bits.  step_counter: device int64 (the
+ * optimizer step of a captured train step; NULL reads 0). */
+int lidbox_input_noise_dropout(float* x, int B, int T, int C, long batch_stride, float stddev, float rate,
+                               unsigned long long seed, const void* step_counter, lidbox_stream_t stream);
 
 /* stream-ordered pitched device-to-device copy / zero fill (hipMemcpy2DAsync / hipMemset2DAsync: memcpy / memset
  * nodes under graph capture): what moves a dense [B, T, C] batch behind the causal pad rows of a layer input. */
@@ -773,6 +780,50 @@ int lidbox_bn_maxpool2d_fwd(const float* x, int B, int T, int F, int C, const fl
                             unsigned char* argmax, lidbox_stream_t stream);
 int lidbox_maxpool2d_bwd(const float* dy, const unsigned char* argmax, int B, int T, int F, int C, float* dx,
                          lidbox_stream_t stream);
+/* ------------------------------------------------------------------ strided Conv2D (lidbox/models/clstm.py:51-60)
+ * Conv2D(C_out, (kt, kf), strides=(1, sf)) with explicit zero padding on the same time-major images x [B][T][F][C_in]:
+ *   y[b, to, fo, co] = bias[co] + sum_{i, j, ci} x[b, to + i - pt0, fo * sf + j - pf0, ci] W[tap(i, j), ci, co]
+ * y [B][To][Fo][C_out], To = T + pt0 + pt1 - kt + 1, Fo = (F + pf0 + pf1 - kf) / sf + 1; x zero outside the image.  W is the
+ * Keras kernel: [kt][kf][C_in][C_out] (tap = i * kf + j) when time_first != 0 (clstm), [kf][kt][C_in][C_out] (tap = j * kt + i,
+ * crnn's orientation) otherwise.  No activation; bias may be NULL; C_out a multiple of 16.  fp32 MFMA implicit GEMM whose tiles
+ * hold one output column, so taps that fall wholly in the padding are not multiplied; each output is one fixed-order sum, the
+ * same whatever B and the utterance's place in the batch.
+ *   _dgrad: dx [B][T][F][C_in] for dy [B][To][Fo][C_out], gathering the (one or two at sf = 6) frequency taps that reach each
+ *           input column; C_in a multiple of 16; workspace: lidbox_conv2d_strided_dgrad_workspace bytes (W transposed per tap).
+ *   _wgrad: dW (Keras layout) and db [C_out] (may be NULL), overwritten; fixed pixel partitions summed in a fixed order
+ *           (bit-identical from run to run); workspace: lidbox_conv2d_strided_wgrad_workspace bytes.
+ * Workspaces 16-byte aligned.  B = 0 is a no-op (wgrad: zeros).  The lidbox_conv2d_* calls above are separate kernels. */
+typedef struct {
+    int kt, kf;        /* taps over time and frequency */
+    int sf;            /* stride over frequency (1 over time) */
+    int pt0, pt1;      /* zero rows before / after the image in time (pt0 < kt) */
+    int pf0, pf1;      /* zero columns before / after in frequency (pf0 < kf) */
+    int time_first;    /* the Keras kernel's first axis: time (1) or frequency (0) */
+} lidbox_conv2d_taps_t;
+int    lidbox_conv2d_strided_fwd(const float* x, int B, int T, int F, int C_in, const float* W, lidbox_conv2d_taps_t taps,
+                                 int C_out, const float* bias, float* y, lidbox_stream_t stream);
+size_t lidbox_conv2d_strided_dgrad_workspace(lidbox_conv2d_taps_t taps, int C_in, int C_out);
+int    lidbox_conv2d_strided_dgrad(const float* dy, int B, int T, int F, int C_in, int C_out, const float* W,
+                                   lidbox_conv2d_taps_t taps, float* dx, void* workspace, size_t workspace_bytes,
+                                   lidbox_stream_t stream);
+size_t lidbox_conv2d_strided_wgrad_workspace(int B, int T, int F, int C_in, int C_out, lidbox_conv2d_taps_t taps);
+int    lidbox_conv2d_strided_wgrad(const float* x, const float* dy, int B, int T, int F, int C_in, int C_out,
+                                   lidbox_conv2d_taps_t taps, float* dW, float* db, void* workspace, size_t workspace_bytes,
+                                   lidbox_stream_t stream);
+/* BatchNormalization apply -> ReLU on x viewed as [R][C]: y = relu(x * scale[c] + shift[c]) (constants of
+ * lidbox_bn_train_stats / lidbox_bn_infer_consts).  _bwd: dx = dy * (x * scale + shift > 0), the gradient of the
+ * BatchNormalization output (in place allowed: dx == dy).  clstm.py:55-56. */
+int lidbox_bn_relu_fwd(const float* x, long R, int C, const float* scale, const float* shift, float* y, lidbox_stream_t stream);
+int lidbox_bn_relu_bwd(const float* x, long R, int C, const float* scale, const float* shift, const float* dy, float* dx,
+                       lidbox_stream_t stream);
+/* BatchNormalization apply -> ReLU -> reduce_max over frequency (clstm.py:58-60) on x [B][T][F][C]: y[b][t][c] =
+ * max_f relu(x * scale + shift), rows of C floats, y_batch_stride floats between utterances.  _bwd: dx [B][T][F][C] = the
+ * gradient of the BatchNormalization output: dy split evenly over every f that ties for the maximum (TF's _MinOrMaxGrad:
+ * (1 / count) * dy), times ReLU's (v > 0), so ties at zero get nothing. */
+int lidbox_bn_relu_maxf_fwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift, float* y,
+                            long y_batch_stride, lidbox_stream_t stream);
+int lidbox_bn_relu_maxf_bwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift,
+                            const float* dy, long dy_batch_stride, float* dx, lidbox_stream_t stream);
 /* kernel_regularizer=l2(lambda) (crnn.py:39) on `count` <= 16 tensors params[offsets[t] .. + sizes[t]): grads (may be NULL)
  * += 2 lambdas[t] grad_scale params, and loss[0] (may be NULL) += sum_t lambdas[t] sum params^2.  A fixed grid writes the
  * gradient and per-workgroup partial sums (workspace: lidbox_l2_penalty_workspace bytes, needed when loss != NULL), a

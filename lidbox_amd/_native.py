@@ -46,6 +46,12 @@ class WeightShadow(C.Structure):
                 ("transpose", C.c_int)]
 
 
+class Conv2DTaps(C.Structure):
+    """lidbox_conv2d_taps_t: taps, frequency stride, explicit pads and kernel orientation of a strided Conv2D"""
+    _fields_ = [("kt", C.c_int), ("kf", C.c_int), ("sf", C.c_int), ("pt0", C.c_int), ("pt1", C.c_int), ("pf0", C.c_int),
+                ("pf1", C.c_int), ("time_first", C.c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise LidboxHipError(
@@ -202,6 +208,16 @@ _SIGS = {
     "lidbox_maxpool2d_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lidbox_l2_penalty_workspace": (_sz, []),
     "lidbox_l2_penalty": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _sz, _vp]),
+    "lidbox_input_noise_dropout": (_i, [_vp, _i, _i, _i, _l, _f, _f, C.c_ulonglong, _vp, _vp]),
+    "lidbox_conv2d_strided_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, Conv2DTaps, _i, _vp, _vp, _vp]),
+    "lidbox_conv2d_strided_dgrad_workspace": (_sz, [Conv2DTaps, _i, _i]),
+    "lidbox_conv2d_strided_dgrad": (_i, [_vp, _i, _i, _i, _i, _i, _vp, Conv2DTaps, _vp, _vp, _sz, _vp]),
+    "lidbox_conv2d_strided_wgrad_workspace": (_sz, [_i, _i, _i, _i, _i, Conv2DTaps]),
+    "lidbox_conv2d_strided_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, Conv2DTaps, _vp, _vp, _vp, _sz, _vp]),
+    "lidbox_bn_relu_fwd": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp]),
+    "lidbox_bn_relu_bwd": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lidbox_bn_relu_maxf_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp]),
+    "lidbox_bn_relu_maxf_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp]),
     "lidbox_seq_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _f, _vp, _l, _vp]),
     "lidbox_seq_avg_pool_bwd": (_i, [_vp, _l, _i, _i, _i, _f, _vp, _l, _l, _i, _vp]),
 }

@@ -421,15 +421,409 @@ int launch_fwd(const float* x, const float* W, const float* bias, int relu, floa
 }
 
 // wgrad partitions: enough workgroups to cover the chip about four times, at least 512 pixels each, at most 1024 partitions
-void wgrad_plan(const ConvGeom& g, int* P, long* per) {
-    const long tiles = lbx_cdiv(g.K, CV_BM) * (g.Cout / conv_tile_n(g.Cout));
+void wgrad_plan_kmn(long K, long M, int Cout, int* P, long* per) {
+    const long tiles = lbx_cdiv(K, CV_BM) * (Cout / conv_tile_n(Cout));
     long p = lbx_cdiv(1024, tiles);
-    p = p < lbx_cdiv(g.M, 512) ? p : lbx_cdiv(g.M, 512);
+    p = p < lbx_cdiv(M, 512) ? p : lbx_cdiv(M, 512);
     p = p < 1024 ? p : 1024;
     p = p > 1 ? p : 1;
-    const long chunks = lbx_cdiv(lbx_cdiv(g.M, CV_KC), p);
+    const long chunks = lbx_cdiv(lbx_cdiv(M, CV_KC), p);
     *per = chunks * CV_KC;
     *P = (int)p;
+}
+
+void wgrad_plan(const ConvGeom& g, int* P, long* per) { wgrad_plan_kmn(g.K, g.M, g.Cout, P, per); }
+
+// ============================================================================================== strided, rectangular Conv2D
+// lidbox/models/clstm.py:51-60: Conv2D(C_out, (kt, kf), strides=(1, sf), padding="same") on the time-major image
+// x [B][T][F][C_in]; explicit zero rows / columns before and after (pt0, pt1, pf0, pf1), so
+//     y[b, to, fo, co] = bias[co] + sum_{i, j, ci} x[b, to + i - pt0, fo sf + j - pf0, ci] W[tap(i, j), ci, co]
+// with To = T + pt0 + pt1 - kt + 1 and Fo = (F + pf0 + pf1 - kf) / sf + 1, and tap(i, j) = i kf + j when the Keras kernel's
+// first axis is time (clstm) or j kt + i when it is frequency (crnn's order).  The tiles are the 128 x BN MFMA tiles above.
+// Forward: a tile is 128 rows (b, to) of ONE output column fo, so its k-chain holds only the frequency taps that land
+// inside the image for that column (at F = 40 conv2d_2 reads 5 of 9 taps per column) -- in the Keras order of the taps,
+// one fixed chain per column: an utterance gives the same bits alone or inside a batch.
+// dgrad: a tile is 128 rows (b, t) of one input column f; the taps that reach it are j = (f + pf0) mod sf + m sf with
+// output column fo = (f + pf0 - j) / sf inside [0, Fo), one or two at sf = 6 -- a gather, no zero insertion.  The kernel
+// is read through a per-tap transposed copy Wt[tap][co][ci] in the workspace (contiguous over the output channels ci).
+// wgrad: rows = kidx (Keras order), contraction over pixels u = (fo, b, to) in fixed partitions as for stride 1; a
+// (tile, partition) pair whose frequency taps all fall in the padding for every column of the partition skips its chunks
+// (the bias tile never skips).  Partials are reduced by the stride-1 reduce kernels: bit-identical from run to run.
+struct SGeom {
+    int B, T, F, Cin, Cout;
+    int To, Fo;
+    int kt, kf, sf, pt, pf;
+    int tfirst;
+    int K;           // kt * kf * Cin
+};
+
+__device__ __forceinline__ int sg_tap(const SGeom& g, int i, int j) { return g.tfirst ? i * g.kf + j : j * g.kt + i; }
+
+// forward: grid (ceil(B To / 128), Fo, Cout / BN).  dgrad (DG): grid (ceil(B T / 128), F, Cin / BN), W = Wt, y = dx.
+template <int BN, bool DG>
+__global__ __launch_bounds__(256) void sconv_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                    const float* __restrict__ bias, float* __restrict__ y, const SGeom g) {
+    constexpr int LDB = cv_ldb<BN>();
+    constexpr int BQ = CV_KC * BN / 256;
+    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int col = blockIdx.y;                      // fo (forward) / f (dgrad)
+    const int n0 = blockIdx.z * BN;
+    const int Rt = DG ? g.T : g.To;                  // rows per utterance of this launch's output
+    const long R = (long)g.B * Rt;
+    const long r0t = (long)blockIdx.x * CV_BM;
+    const int Ncol = DG ? g.Cin : g.Cout;            // output channels
+    const int Kc = DG ? g.Cout : g.Cin;              // contraction channels per tap
+    // the tile's taps: nj frequency taps (j = j0 + jstep * m, m < nj), each with all kt time taps
+    int j0, jstep, nj, fo0 = 0;
+    if (!DG) {
+        const int f0 = col * g.sf - g.pf;
+        j0 = max(0, -f0);
+        nj = max(0, min(g.kf, g.F - f0) - j0);
+        jstep = 1;
+    } else {
+        const int jf = (col + g.pf) % g.sf, q0 = (col + g.pf) / g.sf;
+        const int mlo = max(0, q0 - g.Fo + 1), mhi = min((g.kf - jf + g.sf - 1) / g.sf, q0 + 1);
+        nj = max(0, mhi - mlo);
+        j0 = jf + mlo * g.sf;
+        jstep = g.sf;
+        fo0 = q0 - mlo;                              // output column of tap j0; tap m reads fo0 - m
+    }
+    const int Kv = g.kt * nj * Kc;
+    const int kk = tid & 15, r0 = tid >> 4;
+    int bb[8], tt[8];
+    bool rok[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long r = r0t + r0 + 16 * j;
+        rok[j] = r < R;
+        const long rr = rok[j] ? r : 0;
+        bb[j] = (int)(rr / Rt);
+        tt[j] = (int)(rr - (long)bb[j] * Rt);
+    }
+    // contraction index v -> (time tap i, frequency tap m, channel c) in the Keras order of the taps
+    auto split = [&](int v, int& i, int& m, int& c) {
+        c = v % Kc;
+        const int q = v / Kc;
+        if (g.tfirst) {
+            i = q / nj;
+            m = q - i * nj;
+        } else {
+            m = q / g.kt;
+            i = q - m * g.kt;
+        }
+    };
+    float av[8], bv[BQ];
+    auto load = [&](int kc) {
+        const int v = kc + kk;
+        const bool vok = v < Kv;
+        int i, m, c;
+        split(vok ? v : 0, i, m, c);
+        const int j = j0 + jstep * m;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            if (!DG) {
+                const int t2 = tt[s] + i - g.pt, f2 = col * g.sf + j - g.pf;
+                const bool ok = vok && rok[s] && (unsigned)t2 < (unsigned)g.T;
+                av[s] = ok ? x[(((long)bb[s] * g.T + t2) * g.F + f2) * g.Cin + c] : 0.0f;
+            } else {
+                const int to = tt[s] - i + g.pt, fo = fo0 - m;
+                const bool ok = vok && rok[s] && (unsigned)to < (unsigned)g.To;
+                av[s] = ok ? x[(((long)bb[s] * g.To + to) * g.Fo + fo) * g.Cout + c] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+            const int v2 = kc + kr;
+            float b = 0.0f;
+            if (v2 < Kv) {
+                int i2, m2, c2;
+                split(v2, i2, m2, c2);
+                const long tap = sg_tap(g, i2, j0 + jstep * m2);
+                b = DG ? W[(tap * g.Cout + c2) * g.Cin + n0 + n] : W[(tap * g.Cin + c2) * g.Cout + n0 + n];
+            }
+            bv[q] = b;
+        }
+    };
+    f32x4 acc[2][BN / 16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (Kv > 0) load(0);
+    for (int kc = 0; kc < Kv; kc += CV_KC) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[kk * CV_LDA + r0 + 16 * j] = av[j];
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+            Bs[kr * LDB + n] = bv[q];
+        }
+        __syncthreads();
+        if (kc + CV_KC < Kv) load(kc + CV_KC);
+        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
+    }
+    const int c = lane & 15, q4 = lane >> 4;
+    const int Fcol = DG ? g.F : g.Fo;
+#pragma unroll
+    for (int j = 0; j < BN / 16; ++j) {
+        const int n = n0 + 16 * j + c;
+        const float bb0 = (!DG && bias) ? bias[n] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long row = r0t + w * 32 + 16 * i + 4 * q4 + r;
+                if (row >= R) continue;
+                y[(row * Fcol + col) * Ncol + n] = acc[i][j][r] + bb0;      // row = b Rt + t: pixel (b, t, col)
+            }
+    }
+}
+
+// Wt[tap][co][ci] = W[tap][ci][co]
+__global__ __launch_bounds__(256) void sconv_transpose_kernel(const float* __restrict__ W, float* __restrict__ Wt, int taps,
+                                                              int Cin, int Cout) {
+    const long n = (long)taps * Cin * Cout;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int ci = (int)(i % Cin);
+        const long q = i / Cin;
+        const int co = (int)(q % Cout);
+        const long tap = q / Cout;
+        Wt[i] = W[(tap * Cin + ci) * Cout + co];
+    }
+}
+
+// grid (ceil(K / 128), Cout / BN, P); partition p covers pixels u in [p per, min(M, (p + 1) per)), u = (fo, b, to)
+template <int BN>
+__global__ __launch_bounds__(256) void sconv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                          float* __restrict__ part, float* __restrict__ dbpart, long per,
+                                                          int P, const SGeom g) {
+    constexpr int LDB = cv_ldb<BN>();
+    constexpr int BQ = CV_KC * BN / 256;
+    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int k0 = blockIdx.x * CV_BM, n0 = blockIdx.y * BN, p = blockIdx.z;
+    const long BTo = (long)g.B * g.To, M = BTo * g.Fo;
+    const long mlo = (long)p * per, mhi = min(M, mlo + per);
+    const int kk = tid & 127, p0 = tid >> 7;
+    const bool bias_tile = blockIdx.x == 0;
+    auto tap_of = [&](int kidx, int& i, int& j) {
+        const int tap = kidx / g.Cin;
+        if (g.tfirst) {
+            i = tap / g.kf;
+            j = tap - i * g.kf;
+        } else {
+            j = tap / g.kt;
+            i = tap - j * g.kt;
+        }
+    };
+    const int kidx = k0 + kk;
+    const bool kok = kidx < g.K;
+    int ti, tj;
+    tap_of(kok ? kidx : 0, ti, tj);
+    const int ci = (kok ? kidx : 0) % g.Cin;
+    // skip: no frequency tap of this tile lands inside the image for any column of this partition
+    bool live = bias_tile;
+    if (!live && mlo < mhi) {
+        int jmin = g.kf, jmax = -1;
+        const int klast = min(g.K, k0 + CV_BM) - 1;
+        for (int tap = k0 / g.Cin; tap <= klast / g.Cin; ++tap) {
+            int i, j;
+            tap_of(tap * g.Cin, i, j);
+            jmin = min(jmin, j);
+            jmax = max(jmax, j);
+        }
+        for (int fo = (int)(mlo / BTo); fo <= (int)((mhi - 1) / BTo) && !live; ++fo)
+            live = fo * g.sf + jmax - g.pf >= 0 && fo * g.sf + jmin - g.pf < g.F;
+    }
+    float av[8], bv[BQ];
+    auto load = [&](long mc) {
+        long u = mc + p0;
+        int fo = (int)(u / BTo);
+        long r = u - (long)fo * BTo;
+        int b = (int)(r / g.To), to = (int)(r - (long)b * g.To);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int t2 = to + ti - g.pt, f2 = fo * g.sf + tj - g.pf;
+            const bool ok = u < mhi && kok && (unsigned)t2 < (unsigned)g.T && (unsigned)f2 < (unsigned)g.F;
+            av[j] = ok ? x[(((long)b * g.T + t2) * g.F + f2) * g.Cin + ci] : 0.0f;
+            u += 2;
+            to += 2;
+            while (to >= g.To) {
+                to -= g.To;
+                if (++b == g.B) {
+                    b = 0;
+                    ++fo;
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, pr = e / BN, n = e - pr * BN;
+            const long uu = mc + pr;
+            float v = 0.0f;
+            if (uu < mhi) {
+                const int fo2 = (int)(uu / BTo);
+                const long r2 = uu - (long)fo2 * BTo;       // = b To + to
+                v = dy[(r2 * g.Fo + fo2) * g.Cout + n0 + n];
+            }
+            bv[q] = v;
+        }
+    };
+    f32x4 acc[2][BN / 16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float dbacc = 0.0f;
+    if (live) {
+        if (mlo < mhi) load(mlo);
+        for (long mc = mlo; mc < mhi; mc += CV_KC) {
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 8; ++j) As[(p0 + 2 * j) * CV_LDA + kk] = av[j];
+#pragma unroll
+            for (int q = 0; q < BQ; ++q) {
+                const int e = tid + 256 * q, pr = e / BN, n = e - pr * BN;
+                Bs[pr * LDB + n] = bv[q];
+            }
+            __syncthreads();
+            if (mc + CV_KC < mhi) load(mc + CV_KC);
+            if (bias_tile && tid < BN) {
+#pragma unroll
+                for (int pr = 0; pr < CV_KC; ++pr) dbacc += Bs[pr * LDB + tid];
+            }
+            mma_lds_chunk<BN>(acc, As, Bs, w, lane);
+        }
+    }
+    const int c = lane & 15, q4 = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < BN / 16; ++j) {
+        const int n = n0 + 16 * j + c;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int kr = k0 + w * 32 + 16 * i + 4 * q4 + r;
+                if (kr < g.K) part[((long)kr * g.Cout + n) * P + p] = acc[i][j][r];
+            }
+    }
+    if (bias_tile && tid < BN) dbpart[(long)(n0 + tid) * P + p] = dbacc;
+}
+
+// ---------------------------------------------------------------------------------------------- BN-apply + ReLU (+ max over F)
+// v = x scale[c] + shift[c] (one fmaf, the same expression in every pass so forward and backward agree bit for bit)
+__device__ __forceinline__ float bn_v(float x, float sc, float sh) { return fmaf(x, sc, sh); }
+
+__global__ __launch_bounds__(256) void bn_relu_fwd_kernel(const float* __restrict__ x, long n, int C, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, float* __restrict__ y) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        const float v = bn_v(x[i], scale[c], shift[c]);
+        y[i] = v > 0.0f ? v : 0.0f;
+    }
+}
+
+// dx = dy * (x scale + shift > 0): ReLU's gradient dy (input > 0) with the BatchNormalization output as its input
+__global__ __launch_bounds__(256) void bn_relu_bwd_kernel(const float* __restrict__ x, long n, int C, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, const float* dy, float* dx) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        dx[i] = bn_v(x[i], scale[c], shift[c]) > 0.0f ? dy[i] : 0.0f;
+    }
+}
+
+// y[b][t][c] (ybs floats between utterances, rows of C) = max_f relu(x[b][t][f][c] scale + shift)
+__global__ __launch_bounds__(256) void bn_relu_maxf_fwd_kernel(const float* __restrict__ x, int T, int F, int C,
+                                                               const float* __restrict__ scale, const float* __restrict__ shift,
+                                                               float* __restrict__ y, long ybs, long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        const long r = i / C;                        // b T + t
+        const long b = r / T;
+        const float sc = scale[c], sh = shift[c];
+        const float* p = x + r * F * C + c;
+        float m = 0.0f;
+        for (int f = 0; f < F; ++f) m = fmaxf(m, bn_v(p[(long)f * C], sc, sh));
+        y[b * ybs + (r - b * T) * C + c] = m;
+    }
+}
+
+// TF's _MinOrMaxGrad: dy split evenly over every f whose relu(v) equals the maximum (indicator / count * dy), then ReLU's
+// gradient (v > 0); ties at zero therefore get nothing.  dx [B][T][F][C] = the gradient of the BatchNormalization output.
+__global__ __launch_bounds__(256) void bn_relu_maxf_bwd_kernel(const float* __restrict__ x, int T, int F, int C,
+                                                               const float* __restrict__ scale, const float* __restrict__ shift,
+                                                               const float* __restrict__ dy, long dbs, float* __restrict__ dx,
+                                                               long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        const long r = i / C;
+        const long b = r / T;
+        const float sc = scale[c], sh = shift[c];
+        const float* p = x + r * F * C + c;
+        float m = 0.0f;
+        for (int f = 0; f < F; ++f) m = fmaxf(m, bn_v(p[(long)f * C], sc, sh));
+        int cnt = 0;
+        for (int f = 0; f < F; ++f) {
+            const float v = bn_v(p[(long)f * C], sc, sh);
+            cnt += (v > 0.0f ? v : 0.0f) == m;
+        }
+        const float g = (1.0f / (float)cnt) * dy[b * dbs + (r - b * T) * C + c];
+        float* q = dx + r * F * C + c;
+        for (int f = 0; f < F; ++f) {
+            const float v = bn_v(p[(long)f * C], sc, sh);
+            q[(long)f * C] = (v > 0.0f && v == m) ? g : 0.0f;
+        }
+    }
+}
+
+int sconv_check(const char* fn, int B, int T, int F, int Cin, int Cout, const lidbox_conv2d_taps_t& k) {
+    const long To = (long)T + k.pt0 + k.pt1 - k.kt + 1, Fo = F + k.pf0 + k.pf1 >= k.kf && k.sf >= 1 ? (F + k.pf0 + k.pf1 - k.kf) / k.sf + 1 : 0;
+    const int cmax = Cin > Cout ? Cin : Cout;
+    if (B < 0 || T < 1 || F < 1 || Cin < 1 || Cout < 16 || Cout % 16 != 0 || k.kt < 1 || k.kf < 1 || k.sf < 1 || k.pt0 < 0 ||
+        k.pt1 < 0 || k.pf0 < 0 || k.pf1 < 0 || k.pt0 >= k.kt || k.pf0 >= k.kf || To < 1 || Fo < 1 || Fo > 65535 || F > 65535 ||
+        (long)B * T * F >= (1L << 31) || (long)B * T * F * cmax >= (1L << 40) || (long)B * To * Fo * cmax >= (1L << 40) ||
+        (long)k.kt * k.kf * cmax > (1 << 20)) {
+        lidbox_set_error("%s: invalid argument: B >= 0, T, F, C_in >= 1, C_out a multiple of 16, taps / stride >= 1, pads >= 0 "
+                         "and before < taps, at least one output row and column, sizes in range", fn);
+        return LIDBOX_E_INVALID;
+    }
+    return LIDBOX_OK;
+}
+
+SGeom sgeom(int B, int T, int F, int Cin, int Cout, const lidbox_conv2d_taps_t& k) {
+    SGeom g;
+    g.B = B; g.T = T; g.F = F; g.Cin = Cin; g.Cout = Cout;
+    g.To = T + k.pt0 + k.pt1 - k.kt + 1;
+    g.Fo = (F + k.pf0 + k.pf1 - k.kf) / k.sf + 1;
+    g.kt = k.kt; g.kf = k.kf; g.sf = k.sf; g.pt = k.pt0; g.pf = k.pf0;
+    g.tfirst = k.time_first ? 1 : 0;
+    g.K = k.kt * k.kf * Cin;
+    return g;
+}
+
+template <bool DG>
+int launch_sconv(const float* x, const float* W, const float* bias, float* y, const SGeom& g, hipStream_t st) {
+    const int Ncol = DG ? g.Cin : g.Cout;
+    const int bn = conv_tile_n(Ncol);
+    const dim3 grid((unsigned)lbx_cdiv((long)g.B * (DG ? g.T : g.To), CV_BM), (unsigned)(DG ? g.F : g.Fo), (unsigned)(Ncol / bn));
+    if (bn == 64)
+        hipLaunchKernelGGL((sconv_kernel<64, DG>), grid, dim3(256), 0, st, x, W, bias, y, g);
+    else if (bn == 32)
+        hipLaunchKernelGGL((sconv_kernel<32, DG>), grid, dim3(256), 0, st, x, W, bias, y, g);
+    else
+        hipLaunchKernelGGL((sconv_kernel<16, DG>), grid, dim3(256), 0, st, x, W, bias, y, g);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+int ew_blocks(long n) {
+    const long b = lbx_cdiv(n, 256);
+    return (int)(b < 8192 ? b : 8192);
 }
 
 }  // namespace
@@ -566,5 +960,135 @@ extern "C" int lidbox_l2_penalty(const float* params, float* grads, int count, c
         hipLaunchKernelGGL(l2_loss_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, loss);
         LBX_LAUNCH_OK();
     }
+    return LIDBOX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- strided Conv2D entry points
+extern "C" int lidbox_conv2d_strided_fwd(const float* x, int B, int T, int F, int C_in, const float* W, lidbox_conv2d_taps_t taps,
+                                         int C_out, const float* bias, float* y, lidbox_stream_t stream) {
+    if (int e = sconv_check(__func__, B, T, F, C_in, C_out, taps)) return e;
+    LBX_ARG(x && W && y, "x, W, y != NULL");
+    if (B == 0) return LIDBOX_OK;
+    return launch_sconv<false>(x, W, bias, y, sgeom(B, T, F, C_in, C_out, taps), (hipStream_t)stream);
+}
+
+extern "C" size_t lidbox_conv2d_strided_dgrad_workspace(lidbox_conv2d_taps_t taps, int C_in, int C_out) {
+    if (taps.kt < 1 || taps.kf < 1 || C_in < 1 || C_out < 1) return 0;
+    return (size_t)taps.kt * taps.kf * C_in * C_out * sizeof(float);
+}
+
+extern "C" int lidbox_conv2d_strided_dgrad(const float* dy, int B, int T, int F, int C_in, int C_out, const float* W,
+                                           lidbox_conv2d_taps_t taps, float* dx, void* workspace, size_t workspace_bytes,
+                                           lidbox_stream_t stream) {
+    if (int e = sconv_check(__func__, B, T, F, C_in, C_out, taps)) return e;
+    LBX_ARG(C_in % 16 == 0, "C_in a multiple of 16");
+    LBX_ARG(dy && W && dx, "dy, W, dx != NULL");
+    if (B == 0) return LIDBOX_OK;
+    LBX_ARG(workspace && workspace_bytes >= lidbox_conv2d_strided_dgrad_workspace(taps, C_in, C_out) &&
+                ((uintptr_t)workspace & 15) == 0,
+            "workspace >= lidbox_conv2d_strided_dgrad_workspace() bytes, 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* Wt = (float*)workspace;
+    const long nw = (long)taps.kt * taps.kf * C_in * C_out;
+    hipLaunchKernelGGL(sconv_transpose_kernel, dim3((unsigned)(lbx_cdiv(nw, 256) < 1024 ? lbx_cdiv(nw, 256) : 1024)), dim3(256), 0,
+                       st, W, Wt, taps.kt * taps.kf, C_in, C_out);
+    LBX_LAUNCH_OK();
+    return launch_sconv<true>(dy, Wt, nullptr, dx, sgeom(B, T, F, C_in, C_out, taps), st);
+}
+
+extern "C" size_t lidbox_conv2d_strided_wgrad_workspace(int B, int T, int F, int C_in, int C_out, lidbox_conv2d_taps_t taps) {
+    if (B < 1 || sconv_check(__func__, B, T, F, C_in, C_out, taps) != LIDBOX_OK) return 0;
+    const SGeom g = sgeom(B, T, F, C_in, C_out, taps);
+    int P;
+    long per;
+    wgrad_plan_kmn(g.K, (long)B * g.To * g.Fo, C_out, &P, &per);
+    return (size_t)P * ((size_t)g.K * C_out + C_out) * sizeof(float);
+}
+
+extern "C" int lidbox_conv2d_strided_wgrad(const float* x, const float* dy, int B, int T, int F, int C_in, int C_out,
+                                           lidbox_conv2d_taps_t taps, float* dW, float* db, void* workspace,
+                                           size_t workspace_bytes, lidbox_stream_t stream) {
+    if (int e = sconv_check(__func__, B, T, F, C_in, C_out, taps)) return e;
+    LBX_ARG(x && dy && dW, "x, dy, dW != NULL");
+    hipStream_t st = (hipStream_t)stream;
+    const SGeom g = sgeom(B, T, F, C_in, C_out, taps);
+    const long nw = (long)g.K * C_out;
+    if (B == 0) {
+        LBX_HIP(hipMemsetAsync(dW, 0, nw * sizeof(float), st));
+        if (db) LBX_HIP(hipMemsetAsync(db, 0, C_out * sizeof(float), st));
+        return LIDBOX_OK;
+    }
+    LBX_ARG(workspace && workspace_bytes >= lidbox_conv2d_strided_wgrad_workspace(B, T, F, C_in, C_out, taps) &&
+                ((uintptr_t)workspace & 15) == 0,
+            "workspace >= lidbox_conv2d_strided_wgrad_workspace() bytes, 16-byte aligned");
+    int P;
+    long per;
+    wgrad_plan_kmn(g.K, (long)B * g.To * g.Fo, C_out, &P, &per);
+    float* part = (float*)workspace;
+    float* dbpart = part + (long)P * nw;
+    const int bn = conv_tile_n(C_out);
+    const dim3 grid((unsigned)lbx_cdiv(g.K, CV_BM), (unsigned)(C_out / bn), (unsigned)P);
+    if (bn == 64)
+        hipLaunchKernelGGL(sconv_wgrad_kernel<64>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+    else if (bn == 32)
+        hipLaunchKernelGGL(sconv_wgrad_kernel<32>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+    else
+        hipLaunchKernelGGL(sconv_wgrad_kernel<16>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+    LBX_LAUNCH_OK();
+    const long nout = nw + (db ? C_out : 0);
+    if (P >= 64)
+        hipLaunchKernelGGL(conv_wgrad_reduce_wide_kernel, dim3((unsigned)lbx_cdiv(nout, 4)), dim3(256), 0, st, part, dbpart, P, nw,
+                           nout, dW, db);
+    else
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)lbx_cdiv(nout, 256)), dim3(256), 0, st, part, dbpart, P, nw, nout,
+                           dW, db);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_relu_fwd(const float* x, long R, int C, const float* scale, const float* shift, float* y,
+                                  lidbox_stream_t stream) {
+    LBX_ARG(R >= 0 && C >= 1 && R * C < (1L << 40), "R >= 0, C >= 1");
+    LBX_ARG(x && scale && shift && y, "pointers != NULL");
+    if (R == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(bn_relu_fwd_kernel, dim3(ew_blocks(R * C)), dim3(256), 0, (hipStream_t)stream, x, R * C, C, scale, shift, y);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_relu_bwd(const float* x, long R, int C, const float* scale, const float* shift, const float* dy,
+                                  float* dx, lidbox_stream_t stream) {
+    LBX_ARG(R >= 0 && C >= 1 && R * C < (1L << 40), "R >= 0, C >= 1");
+    LBX_ARG(x && scale && shift && dy && dx, "pointers != NULL");
+    if (R == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(bn_relu_bwd_kernel, dim3(ew_blocks(R * C)), dim3(256), 0, (hipStream_t)stream, x, R * C, C, scale, shift, dy,
+                       dx);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_relu_maxf_fwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift,
+                                       float* y, long y_batch_stride, lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && T >= 1 && F >= 1 && C >= 1 && (long)B * T * F * C < (1L << 40), "B >= 0, T, F, C >= 1");
+    LBX_ARG(y_batch_stride >= (long)T * C, "y_batch_stride >= T * C");
+    LBX_ARG(x && scale && shift && y, "pointers != NULL");
+    const long n = (long)B * T * C;
+    if (n == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(bn_relu_maxf_fwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, T, F, C, scale, shift, y,
+                       y_batch_stride, n);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_relu_maxf_bwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift,
+                                       const float* dy, long dy_batch_stride, float* dx, lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && T >= 1 && F >= 1 && C >= 1 && (long)B * T * F * C < (1L << 40), "B >= 0, T, F, C >= 1");
+    LBX_ARG(dy_batch_stride >= (long)T * C, "dy_batch_stride >= T * C");
+    LBX_ARG(x && scale && shift && dy && dx, "pointers != NULL");
+    const long n = (long)B * T * C;
+    if (n == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(bn_relu_maxf_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, T, F, C, scale, shift, dy,
+                       dy_batch_stride, dx, n);
+    LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

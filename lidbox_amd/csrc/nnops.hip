@@ -1065,6 +1065,30 @@ __global__ __launch_bounds__(256) void spatial_dropout_kernel(float* __restrict_
     }
 }
 
+// GaussianNoise -> channel Dropout (clstm.py:48-49) in place: x = (x + stddev n) * m.  n: Box-Muller over two uniforms of
+// (seed + two fixed offsets, step, b, t C + c); m: spatial_dropout_kernel's draw for (seed, step, b, c), so stddev = 0
+// reproduces that kernel's bits.
+__global__ __launch_bounds__(256) void input_noise_dropout_kernel(float* __restrict__ x, int T, int C, long bs, float stddev,
+                                                                  float rate, unsigned long long seed,
+                                                                  const long long* __restrict__ step) {
+    const int b = blockIdx.y;
+    const unsigned long long stp = step ? (unsigned long long)*step : 0ull;
+    const float keep_scale = 1.f / (1.f - rate);
+    float* xb = x + (long)b * bs;
+    const long total = (long)T * C;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        float v = xb[i];
+        if (stddev != 0.f) {
+            const float u1 = 1.0f - hash_uniform(seed + 0x632BE59BD9B4E019ull, stp, (unsigned)b, (unsigned)i);   // (0, 1]
+            const float u2 = hash_uniform(seed + 0x8CB92BA72F3D8DD7ull, stp, (unsigned)b, (unsigned)i);
+            v += stddev * (sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2));
+        }
+        const float m = hash_uniform(seed, stp, (unsigned)b, (unsigned)c) >= rate ? keep_scale : 0.f;
+        xb[i] = v * m;
+    }
+}
+
 struct RowsOutD {
     float* base;
     long bs, rs;
@@ -1457,6 +1481,21 @@ extern "C" int lidbox_spatial_dropout(float* x, int B, int T, int C, long batch_
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(spatial_dropout_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                        x, T, C, batch_stride, rate, seed, (const long long*)step_counter, mask_out);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_input_noise_dropout(float* x, int B, int T, int C, long batch_stride, float stddev, float rate,
+                                          unsigned long long seed, const void* step_counter, lidbox_stream_t stream) {
+    LBX_ARG(x && B >= 0 && T >= 0 && C >= 1, "x != NULL; C >= 1");
+    LBX_ARG(rate >= 0.f && rate < 1.f && stddev >= 0.f, "0 <= rate < 1, stddev >= 0");
+    LBX_ARG(batch_stride >= (long)T * C && (long)T * C < (1L << 32), "batch_stride >= T * C, T * C < 2^32");
+    LBX_ARG(B <= 65535, "B <= 65535");
+    if (B == 0 || T == 0 || (rate == 0.f && stddev == 0.f)) return LIDBOX_OK;
+    long gx = lbx_cdiv((long)T * C, 256);
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(input_noise_dropout_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       x, T, C, batch_stride, stddev, rate, seed, (const long long*)step_counter);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

@@ -707,6 +707,10 @@ class SequentialTDNN:
                 nv.check(g.nt(dz, Wg, Co, Cd, Co, ntaps * cin, nv.EPI_NONE if grp == 0 else nv.EPI_ACCUM, None, gws, gws_n, st))
         self.join_wgrad()
 
+    def _before_conv(self, ws, i, training, update_moving):
+        """layers a subclass runs between conv i-1 and conv i in forward_ws (models/clstm.py: its 2-D front-end before
+        conv 0, its LSTM before frame4); none here"""
+
     def fused_output_ok(self):
         """the last Dense + log_softmax + sparse cross-entropy (and their backward) can run as lidbox_softmax_head_fwd_bwd:
         few classes, a plain Dense on the fp32 family behind at least one other Dense"""
@@ -732,6 +736,7 @@ class SequentialTDNN:
         cin = self.input_dim
         fresh16 = False                                              # act16[i] holds bf16(act[i]) (written by conv i-1's epilogue)
         for i, c in enumerate(self.convs):
+            self._before_conv(ws, i, training, update_moving)
             if ws.B * ws.Ts[i + 1] > 0 and c.d == 1 and ws.act16[i] is not None:
                 # bf16-storage path: A = bf16 shadow of act[i], B = transposed bf16 kernel; the epilogue also writes the
                 # shadow of act[i+1] when the next conv reads it

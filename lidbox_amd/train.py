@@ -325,7 +325,12 @@ class Trainer:
                 inputs = inputs.contiguous()
             nv.check(lib.lidbox_copy_2d(in_ptr, 4 * in_bs, nv.ptr(inputs), 4 * (inputs.stride(0) if ws.B > 1 else ws.T * C),
                                         4 * ws.T * C, ws.B, st))
-        if model.channel_dropout_rate > 0:
+        if getattr(model, "input_noise_stddev", 0.0) > 0:
+            # GaussianNoise + channel Dropout of a model that declares input noise (clstm.py:48-49), one launch keyed like the
+            # dropout below
+            nv.check(lib.lidbox_input_noise_dropout(in_ptr, ws.B, ws.T, C, in_bs, model.input_noise_stddev,
+                                                    model.channel_dropout_rate, self._dropout_seed(), nv.ptr(self.adam_state), st))
+        elif model.channel_dropout_rate > 0:
             # SpatialDropout1D of the training pass (xvector.py:50-51, cnn.py:29-30); the Adam step counter on the device
             # keys the mask, so every replay of the captured step draws a new one
             nv.check(lib.lidbox_spatial_dropout(in_ptr, ws.B, ws.T, C, in_bs, model.channel_dropout_rate,
