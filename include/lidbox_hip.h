@@ -725,6 +725,27 @@ int lidbox_lstm_fwd(const float* U0, const float* U1, int dirs, int B, int T, in
 int lidbox_lstm_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* cseq,
                     const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
                     lidbox_stream_t stream);
+/* ------------------------------------------------------------------ LSTM recurrence, fused step (lidbox/models/spherespeaker.py:39-41)
+ * The same layer, math, gate order and zg / cseq buffers as lidbox_lstm_fwd / _bwd above, walked the way lidbox_gru_fwd walks
+ * the GRU: one launch per time step for both directions, each workgroup owns 64 rows x 16 units of one direction, computes
+ * its slice of h_{t-1} U (backward: dZ_{t+1} U^T, K = 4H) on fp32 MFMA and applies the cell in the same kernel.  Any H.
+ *   hseq  [B][T+2][h_row_stride], h_row_stride >= dirs*H: h_t of direction d at row t+1, columns d*H.. of the pointer passed;
+ *         rows 0 and T+1 zero and kept zero by the caller.  A layer may so write its output sequence into a column slice of
+ *         a wider buffer (a Concatenate of several layers' outputs costs nothing).
+ *   dh_seq (may be NULL): the gradient of the output sequence, utterances dh_batch_stride and rows dh_row_stride (>= dirs*H)
+ *         floats apart; dh_last (may be NULL) [B][dirs*H] dense: as lidbox_lstm_bwd.
+ *   workspace: lidbox_lstm_step_workspace bytes (backward's carried dc; forward uses none and accepts NULL).
+ * _bwd leaves dZ in zg exactly where lidbox_lstm_bwd leaves it, so dW, dU, db and dX stay the caller's GEMMs.  Forward loads
+ * 16 bytes at a time when H and h_row_stride are multiples of 4 and the pointers 16-byte aligned, 8 bytes when they are
+ * even / 8-byte aligned, 4 bytes otherwise; the k order is the same in all three.  Sums run in a fixed order, no atomics, no
+ * communication between workgroups: a row's results are bit-identical whatever B and its position in the batch.
+ * B = 0 is a no-op. */
+size_t lidbox_lstm_step_workspace(int B, int T, int H, int dirs);
+int lidbox_lstm_step_fwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, float* hseq,
+                         long h_row_stride, float* cseq, void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+int lidbox_lstm_step_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* cseq,
+                         const float* dh_seq, long dh_batch_stride, long dh_row_stride, const float* dh_last,
+                         void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
 /* ------------------------------------------------------------------ GRU recurrence (lidbox/models/bi_gru.py:33-34)
  * tf.keras.layers.GRU with the TF2 defaults (reset_after=True, tanh, sigmoid recurrent activation, use_bias, zero initial
  * state, no dropout, no masking), one or both directions of a Bidirectional(merge_mode="concat") layer in one call (as the

@@ -196,6 +196,9 @@ _SIGS = {
     "lidbox_lstm_workspace": (_sz, [_i, _i, _i, _i]),
     "lidbox_lstm_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lidbox_lstm_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "lidbox_lstm_step_workspace": (_sz, [_i, _i, _i, _i]),
+    "lidbox_lstm_step_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "lidbox_lstm_step_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _l, _vp, _vp, _sz, _vp]),
     "lidbox_gru_workspace": (_sz, [_i, _i, _i, _i]),
     "lidbox_gru_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lidbox_gru_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),

@@ -35,13 +35,20 @@ CHECKPOINT_SUFFIX = ".npz"
 KERAS_HDF5_SUFFIXES = (".hdf5", ".h5")          # what the reference's ModelCheckpoint / save_weights write
 
 
-def read_weights_file(path):
+def read_weights_file(path, blstm_by_wrapper=False):
     """{parameter name: numpy array in the Keras layout} from a checkpoint of this build (.npz) or a Keras HDF5 weight /
-    model file written by the reference (keras_utils.py:57-64: `epoch{epoch:06d}__val_loss{val_loss:.12f}.hdf5`)."""
+    model file written by the reference (keras_utils.py:57-64: `epoch{epoch:06d}__val_loss{val_loss:.12f}.hdf5`).
+    blstm_by_wrapper: name Bidirectional LSTM halves by wrapper and direction in every group of an HDF5 file
+    (`hdf5_reader.keras_param_name`); `read_model_weights` takes it from the model."""
     if path.endswith(KERAS_HDF5_SUFFIXES):
         from .hdf5_reader import load_keras_weights
-        return load_keras_weights(path)
+        return load_keras_weights(path, blstm_by_wrapper=blstm_by_wrapper)
     return dict(np.load(path))
+
+
+def read_model_weights(model, path):
+    """`read_weights_file` with the naming rule the model asks for (its `keras_blstm_by_wrapper` attribute)"""
+    return read_weights_file(path, blstm_by_wrapper=bool(getattr(model, "keras_blstm_by_wrapper", False)))
 
 
 def _set_weights_checked(model, weights, path):
@@ -318,7 +325,7 @@ class KerasWrapper:
                                             key=config["best_checkpoint"]["monitor"], mode=config["best_checkpoint"]["mode"])
         if path is None:
             raise FileNotFoundError("no checkpoint under %s" % os.path.join(experiment_cache, "checkpoints"))
-        _set_weights_checked(model, read_weights_file(path), path)
+        _set_weights_checked(model, read_model_weights(model, path), path)
         return getattr(model_module, "as_embedding_extractor")(model)
 
     def __init__(self, keras_model, model_key, callbacks, loss="sparse_categorical_crossentropy", optimizer=None,
@@ -343,7 +350,7 @@ class KerasWrapper:
     def load_weights(self, path):
         """reference keras_utils.py:186-188"""
         self.initial_epoch = int(parse_checkpoint_value(path, key="epoch"))
-        _set_weights_checked(self.keras_model, read_weights_file(path), path)
+        _set_weights_checked(self.keras_model, read_model_weights(self.keras_model, path), path)
 
     # ------------------------------------------------------------------ fit / evaluate
     def _stage(self, x, y):
