@@ -863,6 +863,31 @@ int lidbox_seq_avg_pool_fwd(const float* x, int B, int T, int C, long batch_stri
 int lidbox_seq_avg_pool_bwd(const float* dout, long ldo, int B, int T, int C, float alpha, float* dx, long batch_stride,
                             long row_stride, int accumulate, lidbox_stream_t stream);
 
+/* Attention pooling of one level of the multi-level attention classifier (multilevel_attention.py:26-33) on the logits
+ * z [B][T][K] of its Dense(K):  p = softmax over k,  c = clip(p, float32(1e-7), float32(1 - 1e-7)),  s[b][k] = sum_t c,
+ * v = sigmoid(z),  att[b][k] = sum_t (c / s) v = (sum_t c v) / s.  att rows are ld_att floats apart (the levels write column
+ * slices of one [B][L K] buffer); colsum [B][K] keeps s for backward.  One pass over z, one workgroup per utterance, fixed
+ * summation order without atomics: utterance b's values depend neither on B nor on b's place in the batch.
+ * _bwd: dz [B][T][K] from datt = d loss / d att (rows ld_datt floats apart), with the pass mask m = (lo <= p <= hi) (a clipped
+ * probability passes no gradient, one equal to a bound does, as TF's _ClipByValueGrad):
+ *   dp = m datt (v - att) / s,   dz = p (dp - sum_j dp_j p_j) + datt (c / s) v (1 - v).
+ * 16-byte loads / stores when K % 4 == 0 and z (and dz) are 16-byte aligned, scalar ones otherwise.  1 <= K <= 1024
+ * (a row lives in the registers of at most 64 lanes), T >= 1; B == 0 returns without a launch. */
+int lidbox_mla_attention_fwd(const float* z, int B, int T, int K, float* att, long ld_att, float* colsum, lidbox_stream_t stream);
+int lidbox_mla_attention_bwd(const float* z, const float* att, long ld_att, const float* colsum, const float* datt, long ld_datt,
+                             int B, int T, int K, float* dz, lidbox_stream_t stream);
+/* BatchNormalization apply -> ReLU -> Dropout(rate) on x viewed as [R][C] in one pass (DenseBlock, multilevel_attention.py:53-57):
+ * y = relu(x * scale[c] + shift[c]) * mask, mask = 0 with probability `rate` and 1 / (1 - rate) otherwise, drawn from
+ * (seed, *step_counter, r, c) exactly as lidbox_dropout_rows draws it (step_counter: device int64, NULL reads 0).
+ * _bwd: dx = (x * scale + shift > 0) ? dy * mask : 0, the gradient of the BatchNormalization output (in place allowed:
+ * dx == dy).  Bit-identical to lidbox_bn_relu_fwd followed by lidbox_dropout_rows on dense rows, and to lidbox_dropout_rows
+ * followed by lidbox_bn_relu_bwd; rate = 0 gives lidbox_bn_relu_*'s bits. */
+int lidbox_bn_relu_dropout_fwd(const float* x, long R, int C, const float* scale, const float* shift, float rate,
+                               unsigned long long seed, const void* step_counter, float* y, lidbox_stream_t stream);
+int lidbox_bn_relu_dropout_bwd(const float* x, long R, int C, const float* scale, const float* shift, float rate,
+                               unsigned long long seed, const void* step_counter, const float* dy, float* dx,
+                               lidbox_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,10 @@ _SIGS = {
     "lidbox_bn_relu_maxf_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp]),
     "lidbox_seq_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _f, _vp, _l, _vp]),
     "lidbox_seq_avg_pool_bwd": (_i, [_vp, _l, _i, _i, _i, _f, _vp, _l, _l, _i, _vp]),
+    "lidbox_mla_attention_fwd": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp]),
+    "lidbox_mla_attention_bwd": (_i, [_vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp]),
+    "lidbox_bn_relu_dropout_fwd": (_i, [_vp, _l, _i, _vp, _vp, _f, C.c_ulonglong, _vp, _vp, _vp]),
+    "lidbox_bn_relu_dropout_bwd": (_i, [_vp, _l, _i, _vp, _vp, _f, C.c_ulonglong, _vp, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():
