@@ -495,6 +495,27 @@ int lidbox_resample(const float* signals, const int64_t* in_starts, const int64_
 int lidbox_fir_filter(const float* signals, const int64_t* starts, const int64_t* lengths, int B, long max_length,
                       const float* coefs, int num_coefs, float* out, lidbox_stream_t stream);
 
+/* data/steps.py:296-307 + features/audio.py:128-148 (third return value): additive noise from a device-resident bank.
+ * Output j (of J) = snr_mixer(utterance src[j], noise_ext, snr_db[j])[2] with noise_ext[i] = clip clip[j] at i mod m, written
+ * at out[out_starts[j] ..], lengths(src[j]) samples.  Utterances: signals / starts / lengths (B of them); clips: bank /
+ * bank_starts / bank_lengths (M of them); several outputs may share an utterance or a clip.  The tiled noise and the two
+ * normalised signals are never written.  Sums are taken in a fixed order that depends on the utterance's length only: an
+ * output is bit-identical whatever else the call holds.  Utterances of up to 65536 samples are read once (registers and LDS),
+ * longer ones (up to 2^21) three times in tiles, with workspace.  Starts need not be aligned; aligned ones take 16-byte
+ * accesses.  The lengths and indexes come twice: as HOST arrays for checking and planning, and as DEVICE arrays for the
+ * kernels.  Invalid: an index out of range, a referenced clip that is empty, an utterance beyond 2^21 samples.
+ * workspace: >= lidbox_mix_noise_workspace(longest utterance, J) bytes, 8-byte aligned, no initialisation. */
+size_t lidbox_mix_noise_workspace(long max_length, int J);
+int lidbox_mix_noise(const float* signals, const int64_t* starts, const int64_t* lengths, const float* bank,
+                     const int64_t* bank_starts, const int64_t* bank_lengths, const int32_t* src, const int32_t* clip,
+                     const float* snr_db, float* out, const int64_t* out_starts, const int64_t* lengths_host,
+                     const int64_t* bank_lengths_host, const int32_t* src_host, const int32_t* clip_host, int B, int M, int J,
+                     void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+/* data/steps.py:966 tf.tile per utterance: out[out_starts[b] + i] = utterance b at i mod lengths[b], i < reps[b] * lengths[b]
+ * (reps int64 in device memory; 0 repeats or an empty utterance write nothing).  max_out_length: the longest output (host). */
+int lidbox_signal_tile(const float* signals, const int64_t* starts, const int64_t* lengths, const int64_t* reps, float* out,
+                       const int64_t* out_starts, int B, long max_out_length, lidbox_stream_t stream);
+
 /* lidbox/util.py:41-57 merge_chunk_predictions with the default stack_and_average: x [rows, D] sorted so that
  * the rows of segment s are segment_offsets[s] .. segment_offsets[s+1] (int64, device); out [num_segments, D]. */
 int lidbox_segment_mean(const float* x, const int64_t* segment_offsets, int num_segments, int D, float* out,

@@ -145,6 +145,9 @@ _SIGS = {
     "lidbox_resample_workspace": (_sz, [_vp, _vp, _i]),
     "lidbox_resample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "lidbox_fir_filter": (_i, [_vp, _vp, _vp, _i, _l, _vp, _i, _vp, _vp]),
+    "lidbox_mix_noise_workspace": (_sz, [_l, _i]),
+    "lidbox_mix_noise": (_i, [_vp] * 15 + [_i, _i, _i, _vp, _sz, _vp]),
+    "lidbox_signal_tile": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _vp]),
     "lidbox_freq_attention_fwd": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
     "lidbox_freq_attention_bwd": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp]),
     "lidbox_log_softmax_fwd": (_i, [_vp, _i, _i, _vp, _vp]),

@@ -1,14 +1,25 @@
 """
-Counterpart of the lidbox.data.steps entries on and next to the hot path.  `ds` is any iterable of element
-dicts (the reference maps the same functions over a tf.data.Dataset); results are generators of dicts.
+Counterpart of lidbox.data.steps.  `ds` is any iterable of element dicts (the reference maps the same functions over a
+tf.data.Dataset); results are generators of dicts.  `from_steps` turns a list of `Step`s -- what
+`lidbox_amd.data.pipelines.create_dataset` makes of a lidbox config -- into such a generator.
 
+  device steps
   extract_features      reference steps.py:708-736   (the hot path's boundary)
   compute_rms_vad       reference steps.py:417-432   energy VAD decisions             
   apply_vad             reference steps.py:183-200   drop the non-speech frames        
   create_signal_chunks  reference steps.py:579-632   fixed-length chunks, new ids      
   random_signal_speed_change   reference steps.py:331-352   Fourier resampling at a random speed ratio
   random_signal_fir_filtering  reference steps.py:355-368   random N(0, 1) FIR filter per signal
+  augment_by_additive_noise    reference steps.py:235-328   noise clips from a device-resident bank mixed in at random SNRs
+  augment_signals       reference steps.py:215-229   originals and augmented copies, sampled at random
+  repeat_too_short_signals     reference steps.py:950-969   tile signals up to a minimum length
+  create_input_chunks   reference steps.py:558-576   windows of `input` frames, new ids
+  normalize             reference steps.py:821-834   batched CMVN of one key
   extract_embeddings    reference steps.py:674-705   batched embedding extraction      
+  load_audio            reference steps.py:803-818   WAV files -> `signal`, `sample_rate`
+
+  host steps
+  initialize, drop_empty, apply_filters, remap_keys, filter_keys_in_set, as_supervised, shuffle, lambda
 
 The signal steps gather `launch_batch` elements into one ragged device batch per kernel launch
 (lidbox_amd/features/signal_ops.py); the order of elements is preserved.
@@ -24,14 +35,20 @@ schema (`_feature_extraction_kwargs_to_args`, steps.py:94-104):
 The reference maps this over a tf.data.Dataset (batch -> map -> unbatch); here `ds` is any
 iterable of element dicts holding at least `signal` (1-D float32 tensor or array) and
 `sample_rate`, and the result is a generator of the same dicts with `input` ([T, C] tensor on the
-HIP device) and `feature_type` added.  Everything else in lidbox.data.steps (tf.data plumbing,
-file-based augmentation, caching, TensorBoard dumps) is out of scope.
+HIP device) and `feature_type` added.  Not built: WebRTC VAD, Kaldi I/O, WAV header checks, on-disk caching,
+TensorBoard dumps and the debug / statistics steps; `from_steps` names them instead of skipping them.
 """
+import collections
+import itertools
 import logging
+import os
+import shutil
 
 import numpy as np
 import torch
 
+from .. import features
+from .. import iter_metadata_file
 from ..features import audio as audio_features
 from ..features import signal_ops
 from . import tf_utils
@@ -279,6 +296,207 @@ def random_signal_fir_filtering(ds, num_coefs=10, flag=None, seed=None, launch_b
         yield from _augmented(batch, idx, signal_ops.fir_filter(r, torch.from_numpy(coefs)).split())
 
 
+# ------------------------------------------------------------------ additive noise (csrc/mix_noise.hip)
+def noise_paths_by_type(noise_datadir):
+    """steps.py:252-256: `noise_datadir/id2label` (noise id, noise type) and `id2path` (noise id, path) ->
+    {noise type: [paths]} in file order.  Host only."""
+    id2type = dict(iter_metadata_file(os.path.join(noise_datadir, "id2label"), 2))
+    type2paths = collections.OrderedDict()
+    for noise_id, path in iter_metadata_file(os.path.join(noise_datadir, "id2path"), 2):
+        type2paths.setdefault(id2type[noise_id], []).append(path)
+    return type2paths
+
+
+def additive_noise_draws(rng, snr_list, type_counts):
+    """the draws of steps.py:281-285 for ONE element: for every (noise_type, snr_low, snr_high) of snr_list, in order, first
+    the clip index rng.integers(0, type_counts[noise_type]), then snr = low + (high - low) * rng.random(float32) in float32
+    -> [(noise_type, index, snr)]"""
+    draws = []
+    for noise_type, snr_low, snr_high in snr_list:
+        if noise_type not in type_counts:
+            raise KeyError("noise type %r of snr_list is not in the noise directory (types: %s)"
+                           % (noise_type, ", ".join(sorted(type_counts))))
+        count = int(type_counts[noise_type])
+        if count < 1:
+            raise ValueError("noise type %r has no clips" % (noise_type,))
+        index = int(rng.integers(0, count))
+        u = rng.random(dtype=np.float32)
+        snr = np.float32(np.float32(snr_low) + (np.float32(snr_high) - np.float32(snr_low)) * u)
+        draws.append((noise_type, index, snr))
+    return draws
+
+
+def additive_noise_id(utt_id, noise_type, snr):
+    """steps.py:309-316: "augmented-<id>-<noise type>-snr<snr with two decimals>" """
+    if isinstance(utt_id, bytes):
+        utt_id = utt_id.decode("utf-8")
+    return "augmented-%s-%s-snr%.2f" % (utt_id, noise_type, float(np.float32(snr)))
+
+
+def _copy_noise_files_to_tmpdir(type2paths):
+    """steps.py:258-269"""
+    tmpdir = os.path.join(os.environ.get("TMPDIR", "/tmp"), "lidbox_noise_signals")
+    logger.info("Copying all noise files to TMPDIR '%s'", tmpdir)
+    copied = collections.OrderedDict()
+    for noise_type, paths in type2paths.items():
+        copied[noise_type] = []
+        for src in paths:
+            dst = os.path.join(tmpdir, noise_type, os.path.basename(src))
+            logger.debug("%s -> %s", src, dst)
+            os.makedirs(os.path.dirname(dst), exist_ok=True)
+            shutil.copyfile(src, dst)
+            copied[noise_type].append(dst)
+    return copied
+
+
+def augment_by_additive_noise(ds, noise_datadir, snr_list, copy_noise_files_to_tmpdir=False, seed=None, launch_batch=256):
+    """reference steps.py:235-328.  Every element yields len(snr_list) NEW elements, in snr_list order, and not itself: its
+    signal mixed (audio.snr_mixer, third value) with a clip of the given noise type drawn from `noise_datadir`, repeated to the
+    signal's length, at an SNR drawn from [snr_low, snr_high]; `id` becomes `additive_noise_id(...)`, other keys are carried.
+    All clips are read once into one bank on the device.  Draws: one np.random.default_rng(seed) per call,
+    `additive_noise_draws` per element in element order, so the output does not depend on launch_batch.
+    Returns None (after logging the reference's error) when `noise_datadir` does not exist."""
+    logger.info("Augmenting dataset with additive noise from '%s'.", noise_datadir)
+    if not os.path.isdir(noise_datadir):
+        logger.error("Noise source dir '%s' does not exist.", noise_datadir)
+        return None
+    type2paths = noise_paths_by_type(noise_datadir)
+    snr_list = [tuple(s) for s in snr_list]
+    for noise_type, _, _ in snr_list:
+        if noise_type not in type2paths:
+            raise KeyError("noise type %r of snr_list is not in '%s' (types: %s)"
+                           % (noise_type, noise_datadir, ", ".join(sorted(type2paths))))
+    if copy_noise_files_to_tmpdir:
+        type2paths = _copy_noise_files_to_tmpdir(type2paths)
+    clips, rates, first = [], [], {}
+    for noise_type, paths in type2paths.items():
+        first[noise_type] = len(clips)
+        for path in paths:
+            signal, rate = audio_features.read_wav(path)
+            clips.append(signal)
+            rates.append(int(rate))
+    bank = signal_ops.RaggedSignals.from_list(clips)
+    type_counts = {t: len(p) for t, p in type2paths.items()}
+    rng = np.random.default_rng(seed)
+
+    def mixed():
+        for batch in _launch_batches(ds, launch_batch):
+            src, clip, snrs, ids = [], [], [], []
+            for i, x in enumerate(batch):
+                for noise_type, index, snr in additive_noise_draws(rng, snr_list, type_counts):
+                    k = first[noise_type] + index
+                    if rates[k] != int(x["sample_rate"]):                                            # steps.py:294
+                        raise ValueError("Invalid noise signals are being used, all noise signals must have same sample rate "
+                                         "as speech signals that are being augmented (clip '%s' has %d Hz, element %r %d Hz)"
+                                         % (type2paths[noise_type][index], rates[k], x.get("id"), int(x["sample_rate"])))
+                    src.append(i)
+                    clip.append(k)
+                    snrs.append(snr)
+                    ids.append(additive_noise_id(x["id"], noise_type, snr))
+            r = signal_ops.RaggedSignals.from_list([x["signal"] for x in batch])
+            out = signal_ops.mix_noise(r, bank, src, clip, snrs).split()
+            for i, new_id, signal in zip(src, ids, out):
+                yield dict(batch[i], id=new_id, signal=signal)
+
+    return mixed()
+
+
+def augment_signals(ds, augment_configs, seed=None):
+    """reference steps.py:215-229: one augmented dataset per config (`type` "additive_noise" -> augment_by_additive_noise
+    with the config's other keys, `split` aside, as keyword arguments), then elements are drawn from [ds] + augmented like
+    tf.data.experimental.sample_from_datasets: at each draw one of the sources that are not exhausted is chosen uniformly
+    (np.random.default_rng(seed)), so every source keeps its own order and the output is exactly the union.
+    `ds` is iterated once: every source reads its own itertools.tee branch, which buffers only what the others have not
+    consumed yet (at most one launch batch)."""
+    branches = list(itertools.tee(ds, 1 + len(augment_configs)))
+    sources = [branches[0]]
+    for conf, branch in zip(augment_configs, branches[1:]):
+        aug_kwargs = {k: v for k, v in conf.items() if k not in {"type", "split"}}
+        if conf["type"] == "random_resampling":
+            # the reference calls augment_by_random_resampling here, a function it never defines (steps.py:223)
+            raise ValueError("augmentation type 'random_resampling' is not defined by lidbox; use the step "
+                             "'random_signal_speed_change' instead")
+        elif conf["type"] == "additive_noise":
+            augmented = augment_by_additive_noise(branch, **aug_kwargs)
+            if augmented is not None:
+                sources.append(augmented)
+        else:
+            logger.warning("Unknown signal augmentation type '%s', skipping", conf["type"])
+    rng = np.random.default_rng(seed)
+
+    def sampled():
+        live = [iter(s) for s in sources]
+        while live:
+            i = int(rng.integers(0, len(live)))
+            try:
+                yield next(live[i])
+            except StopIteration:
+                del live[i]
+
+    return sampled()
+
+
+def repeat_count(min_length_ms, sample_rate, num_samples):
+    """steps.py:961-966 in the reference's float32: int(ceil(divide_no_nan(float32(1e-3 * ms) * float32(rate), float32(n))))"""
+    target = np.float32(1e-3 * min_length_ms) * np.float32(sample_rate)
+    n = np.float32(num_samples)
+    ratio = np.float32(0.0) if n == 0 else np.float32(target / n)
+    return int(np.ceil(ratio))
+
+
+def repeat_too_short_signals(ds, min_length_ms, launch_batch=256):
+    """reference steps.py:950-969: every signal is repeated `repeat_count` times (signal_ops.tile), which makes it at least
+    min_length_ms long; a signal that is long enough already (one repeat) and an empty one are passed on as they are."""
+    logger.info("Repeating all signals until they are at least %d ms", min_length_ms)
+    for batch in _launch_batches(ds, launch_batch):
+        sigs = [torch.as_tensor(x["signal"]) for x in batch]
+        reps = [repeat_count(min_length_ms, x["sample_rate"], s.numel()) for x, s in zip(batch, sigs)]
+        if min(reps) < 0:
+            raise ValueError("min_length_ms = %r gives a negative repeat count" % (min_length_ms,))
+        idx = [i for i, (s, k) in enumerate(zip(sigs, reps)) if s.numel() and k != 1]
+        if not idx:
+            yield from batch
+            continue
+        r = signal_ops.RaggedSignals.from_list([sigs[i] for i in idx])
+        yield from _augmented(batch, idx, signal_ops.tile(r, [reps[i] for i in idx]).split())
+
+
+# ------------------------------------------------------------------ steps on `input`
+def create_input_chunks(ds, length, step, launch_batch=256):
+    """reference steps.py:558-576: `input` [T, C] becomes its max(0, 1 + (T - length) // step) windows of `length` frames
+    (signal_ops.input_chunks); `id` gets "-%06d" with the 1-based window number, other keys are carried; elements
+    with T < length vanish."""
+    for batch in _launch_batches(ds, launch_batch):
+        by_width = {}
+        for i, x in enumerate(batch):
+            by_width.setdefault(int(x["input"].shape[1]), []).append(i)
+        chunks_of = [None] * len(batch)
+        for idx in by_width.values():
+            chunks, nch = signal_ops.input_chunks([batch[i]["input"] for i in idx], length, step)
+            c0 = 0
+            for i, n in zip(idx, nch):
+                chunks_of[i] = chunks[c0:c0 + int(n)]
+                c0 += int(n)
+        for x, ch in zip(batch, chunks_of):
+            for k in range(ch.shape[0]):
+                yield dict(x, id="%s-%06d" % (x["id"], k + 1), input=ch[k])
+
+
+def normalize(ds, config):
+    """reference steps.py:821-834: batches of config.get("batch_size", 1) elements, features.cmvn(x[key], **kwargs) on the
+    stacked batch, unbatched.  Elements of one batch must share the shape (tf.data's `batch` has the same requirement)."""
+    logger.info("Applying normalization with config:\n  %s", _dict_to_logstring(config))
+    key = config["key"]
+    kwargs = config.get("kwargs", {})
+    for batch in _launch_batches(ds, int(config.get("batch_size", 1))):
+        values = [torch.as_tensor(x[key]) for x in batch]
+        if any(v.shape != values[0].shape for v in values):
+            raise ValueError("cannot batch '%s' tensors of different shapes for normalization" % key)
+        normalized = features.cmvn(torch.stack(values), **kwargs)
+        for x, v in zip(batch, normalized.unbind(0)):
+            yield dict(x, **{key: v})
+
+
 # ------------------------------------------------------------------ embeddings (SURVEY 8f.2)
 def extract_embeddings(ds, config):
     """reference steps.py:674-705.  config = {"extractors": [...], "batch_size": 1, "no_unbatch": False}.
@@ -315,3 +533,199 @@ def extract_embeddings(ds, config):
         else:
             for i, x in enumerate(batch):
                 yield dict(x, embedding=embeddings[i])
+
+
+# ------------------------------------------------------------------ host steps and the step list driver
+Step = collections.namedtuple("Step", ("key", "kwargs"))
+
+
+def _dict_to_logstring(d):
+    return "\n  ".join("{}: {}".format(k, p) for k, p in d.items())
+
+
+def _size(v):
+    return int(v.numel()) if isinstance(v, torch.Tensor) else int(np.size(v))
+
+
+def _all_true(v):
+    return bool(v.all()) if isinstance(v, (torch.Tensor, np.ndarray)) else bool(v)
+
+
+def initialize(labels, init_data):
+    """reference steps.py:776-800: one element per utterance from the metadata columns of `init_data`, plus `target` = the
+    index of its `label` in `labels` (len(labels) for a label that is not listed, as the reference's lookup table)."""
+    init_data = {k: list(v) for k, v in init_data.items()}
+    logger.info("Initializing dataset from metadata:\n  %s",
+                "\n  ".join("{}: {}".format(k, len(init_data[k])) for k in sorted(init_data)))
+    sizes = {len(v) for v in init_data.values()}
+    if len(sizes) != 1:
+        logger.error("Cannot initialize dataset from metadata dictionary that has values of different lengths")
+        return None
+    label2int = {label: i for i, label in enumerate(labels)}
+    count = sizes.pop()
+
+    def elements():
+        for i in range(count):
+            x = {k: v[i] for k, v in init_data.items()}
+            yield dict(x, target=label2int.get(x["label"], len(label2int)))
+
+    return elements()
+
+
+def load_audio(ds, num_prefetch=None):
+    """reference steps.py:803-818: `signal` (float32 on the HIP device) and `sample_rate` from the WAV file at `path`.
+    `num_prefetch` is accepted for the config's sake; elements are produced on demand."""
+    logger.info("Reading audio files from the path of each element and appending the read signals and their sample rates "
+                "to each element.")
+    for x in ds:
+        signal, sample_rate = audio_features.read_wav(x["path"])
+        yield dict(x, signal=signal, sample_rate=sample_rate)
+
+
+def drop_empty(ds):
+    """reference steps.py:635-650: drop elements whose `signal` or `input` has no entries"""
+    non_scalar_keys = ("signal", "input")
+    logger.info("Dropping every element which have an empty tensor at any of the non-scalar element keys:\n  %s",
+                "\n  ".join(non_scalar_keys))
+    return (x for x in ds if not any(k in x and _size(x[k]) == 0 for k in non_scalar_keys))
+
+
+def apply_filters(ds, config):
+    """reference steps.py:137-180: keep the elements that pass every filter of `config`: `equal` {key, value},
+    `min_signal_length_ms` (threshold int(float32(sample_rate) * float32(1e-3 * ms)) samples, steps.py:154-157) and
+    `min_shape` {key, shape}.  A filter passes elements that do not have its key."""
+    logger.info("Applying filters on every element in the dataset, keeping only elements which match the given config:\n  %s",
+                _dict_to_logstring(config))
+    filters = []
+    if "equal" in config:
+        key, value = config["equal"]["key"], config["equal"]["value"]
+        filters.append((lambda x, k=key, v=value: k not in x or _all_true(x[k] == v), key))
+    if "min_signal_length_ms" in config:
+        min_sec = np.float32(1e-3 * config["min_signal_length_ms"])
+        filters.append((lambda x, v=min_sec: "signal" not in x or _size(x["signal"]) >= int(np.float32(x["sample_rate"]) * v),
+                        "min_signal_length_sec"))
+    if "min_shape" in config:
+        key, shape = config["min_shape"]["key"], tuple(config["min_shape"]["shape"])
+        filters.append((lambda x, k=key, v=shape: k not in x or (len(x[k].shape) == len(v) and
+                                                                 all(a >= b for a, b in zip(x[k].shape, v))), key))
+    if not filters:
+        logger.warning("No filters defined, skipping filtering")
+        return ds
+    logger.info("Using %d different filters:\n  %s", len(filters), "\n  ".join(name for _, name in filters))
+    return (x for x in ds if all(fn(x) for fn, _ in filters))
+
+
+def remap_keys(ds, new_keys):
+    """reference steps.py:938-947: rename keys; a key mapped to None is dropped"""
+    logger.info("Remapping keys of every element using config:\n  %s", _dict_to_logstring(new_keys))
+    return ({new_keys.get(k, k): v for k, v in x.items() if new_keys.get(k, k) is not None} for x in ds)
+
+
+def filter_keys_in_set(ds, keys):
+    """reference steps.py:739-748"""
+    logger.info("For each element in the dataset, keeping only values with keys: %s.", ", ".join(keys))
+    return ({k: v for k, v in x.items() if k in keys} for x in ds)
+
+
+def as_supervised(ds):
+    """reference steps.py:203-212: (input, target) pairs"""
+    logger.info("Converting all elements to tuple pairs (inputs, targets) and dropping all other values.")
+    return ((x["input"], x["target"]) for x in ds)
+
+
+def shuffle(ds, buffer_size, seed=None):
+    """reference steps.py:997-999 (tf.data's buffered shuffle): a buffer of `buffer_size` elements is kept full; every output
+    is drawn uniformly from it (np.random.default_rng(seed))"""
+    logger.info("Shuffling dataset with buffer size %d", buffer_size)
+    buffer_size = int(buffer_size)
+    if buffer_size < 1:
+        raise ValueError("buffer_size must be at least 1")
+    rng = np.random.default_rng(seed)
+
+    def shuffled():
+        buf = []
+        for x in ds:
+            if len(buf) < buffer_size:
+                buf.append(x)
+                continue
+            i = int(rng.integers(0, buffer_size))
+            yield buf[i]
+            buf[i] = x
+        while buf:
+            i = int(rng.integers(0, len(buf)))
+            buf[i], buf[-1] = buf[-1], buf[i]
+            yield buf.pop()
+
+    return shuffled()
+
+
+def lambda_fn(ds, fn):
+    """reference steps.py:837-842"""
+    logger.info("Applying function '%s' on dataset.", str(fn))
+    return fn(ds)
+
+
+def _pass_through(key):
+    def step(ds, **kwargs):
+        logger.warning("Step '%s' is not built in lidbox_amd; it does not alter elements, the dataset is passed on as it is.", key)
+        return ds
+    return step
+
+
+VALID_STEP_FUNCTIONS = {
+    "apply_filters": apply_filters,
+    "apply_vad": apply_vad,
+    "as_supervised": as_supervised,
+    "augment_by_additive_noise": augment_by_additive_noise,
+    "augment_signals": augment_signals,
+    "cache": _pass_through("cache"),
+    "compute_rms_vad": compute_rms_vad,
+    "consume": _pass_through("consume"),
+    "consume_to_tensorboard": _pass_through("consume_to_tensorboard"),
+    "create_input_chunks": create_input_chunks,
+    "create_signal_chunks": create_signal_chunks,
+    "drop_empty": drop_empty,
+    "extract_embeddings": extract_embeddings,
+    "extract_features": extract_features,
+    "filter_keys_in_set": filter_keys_in_set,
+    "initialize": initialize,
+    "lambda": lambda_fn,
+    "load_audio": load_audio,
+    "normalize": normalize,
+    "random_signal_fir_filtering": random_signal_fir_filtering,
+    "random_signal_speed_change": random_signal_speed_change,
+    "remap_keys": remap_keys,
+    "repeat_too_short_signals": repeat_too_short_signals,
+    "shuffle": shuffle,
+}
+
+
+def from_steps(steps):
+    """reference steps.py:34-58: initialize(**steps[0].kwargs), then every further step applied in order.  A step that
+    is None is skipped.  Unlike the reference, which logs an unknown key and goes on, a key without a function here raises
+    ValueError: dropping e.g. a VAD step silently would change the data."""
+    logger.info("Initializing and preparing dataset from %d steps:\n  %s", len(steps),
+                "\n  ".join(s.key for s in steps if s is not None))
+    if steps[0] is None or steps[0].key != "initialize":
+        logger.critical("When constructing a dataset, the first step must be 'initialize' but it was '%s'. The 'initialize' step "
+                        "is needed for first loading all metadata such as the utterance_id to wavpath mappings.",
+                        None if steps[0] is None else steps[0].key)
+        return None
+    for step in steps[1:]:
+        if step is not None and step.key not in VALID_STEP_FUNCTIONS:
+            raise ValueError("step '%s' is not implemented in lidbox_amd.data.steps" % step.key)
+    ds = initialize(**steps[0].kwargs)
+    if ds is None:
+        logger.critical("Failed to apply step 'initialize', it did not return a dataset.")
+        return None
+    for step_num, step in enumerate(steps[1:], start=2):
+        if step is None:
+            logger.warning("Skipping no-op step with value None")
+            continue
+        logger.info("Applying step number %d: '%s'.", step_num, step.key)
+        ds = VALID_STEP_FUNCTIONS[step.key](ds, **step.kwargs)
+        if ds is None:
+            logger.critical("Failed to apply step '%s', it did not return a dataset.", step.key)
+            return None
+    logger.info("All %d steps completed, returning prepared dataset.", len(steps))
+    return ds

@@ -1,7 +1,8 @@
 """
 Ragged-batch driver for the signal kernels of csrc/signal.hip: energy VAD, VAD application,
 fixed-length chunking, peak normalisation, RMS and the SNR mixer for MANY variable-length signals per launch;
-and of csrc/augment.hip: Fourier resampling (speed change) and per-utterance FIR filtering.
+and of csrc/augment.hip: Fourier resampling (speed change) and per-utterance FIR filtering;
+and of csrc/mix_noise.hip: additive noise from a device-resident bank of clips, and tiling.
 `lidbox_amd.features.audio` (single-signal functions with the reference's names) and
 `lidbox_amd.data.steps` (dataset steps) are thin layers over this module.
 
@@ -266,3 +267,96 @@ def fir_filter(r, coefs):
         nv.check(nv.lib.lidbox_fir_filter(nv.ptr(r.flat), nv.ptr(r.starts), nv.ptr(r.lengths), r.B, max_len, nv.ptr(f),
                                           int(f.shape[1]), nv.ptr(out), nv.current_stream()))
     return RaggedSignals(out, r.starts_host, r.lengths_host)
+
+
+# ------------------------------------------------------------------ additive noise, tiling, input chunks (csrc/mix_noise.hip)
+MAX_MIX_LENGTH = 1 << 21         # samples per utterance of lidbox_mix_noise
+
+
+def mix_noise(r, bank, src, clip, snr_db):
+    """steps.py:296-307 + audio.py:128-148 for J outputs: output j = snr_mixer(utterance src[j] of r, clip clip[j] of bank
+    repeated to the utterance's length, snr_db[j])[2].  `bank` is a RaggedSignals of noise clips that stays on the device;
+    several outputs may share an utterance or a clip.  -> new RaggedSignals of J signals with 16-byte aligned starts.
+    An output's bits do not depend on what else is in the call."""
+    dev = r.flat.device
+    if bank.flat.device != dev:
+        raise ValueError("the noise bank is on %s, the signals on %s" % (bank.flat.device, dev))
+    src_h = np.ascontiguousarray(np.asarray(src, np.int64).reshape(-1))
+    clip_h = np.ascontiguousarray(np.asarray(clip, np.int64).reshape(-1))
+    snr_h = np.ascontiguousarray(np.asarray(snr_db, np.float32).reshape(-1))
+    J = len(src_h)
+    if len(clip_h) != J or len(snr_h) != J:
+        raise ValueError("src, clip and snr_db must have one entry per output")
+    if J and (src_h.min() < 0 or src_h.max() >= r.B):
+        raise ValueError("utterance index out of range 0 .. %d" % (r.B - 1))
+    if J and (clip_h.min() < 0 or clip_h.max() >= bank.B):
+        raise ValueError("noise clip index out of range 0 .. %d" % (bank.B - 1))
+    lengths = r.lengths_host[src_h] if J else np.zeros(0, np.int64)
+    starts, total = _aligned_starts(lengths)
+    out = torch.zeros(max(total, ALIGN), dtype=torch.float32, device=dev)
+    if J:
+        src32, clip32 = src_h.astype(np.int32), clip_h.astype(np.int32)
+        n_h, m_h = np.ascontiguousarray(r.lengths_host), np.ascontiguousarray(bank.lengths_host)
+        with torch.cuda.device(dev):
+            wbytes = nv.lib.lidbox_mix_noise_workspace(int(lengths.max()), J)
+            ws = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+            src_d, clip_d = torch.from_numpy(src32).to(dev), torch.from_numpy(clip32).to(dev)
+            snr_d, starts_d = torch.from_numpy(snr_h).to(dev), torch.from_numpy(starts).to(dev)
+            nv.check(nv.lib.lidbox_mix_noise(nv.ptr(r.flat), nv.ptr(r.starts), nv.ptr(r.lengths), nv.ptr(bank.flat),
+                                             nv.ptr(bank.starts), nv.ptr(bank.lengths), nv.ptr(src_d), nv.ptr(clip_d),
+                                             nv.ptr(snr_d), nv.ptr(out), nv.ptr(starts_d), n_h.ctypes.data, m_h.ctypes.data,
+                                             src32.ctypes.data, clip32.ctypes.data, r.B, bank.B, J, nv.ptr(ws), wbytes,
+                                             nv.current_stream()))
+    return RaggedSignals(out, starts, lengths)
+
+
+def tile(r, reps):
+    """tf.tile(signal, [reps]) per utterance (steps.py:966): out[b][i] = in[b][i mod n_b], i < reps[b] * n_b, a bit-exact copy
+    -> new RaggedSignals with 16-byte aligned starts; reps[b] = 0 or an empty utterance gives an empty signal"""
+    dev = r.flat.device
+    reps_h = np.ascontiguousarray(np.asarray(reps, np.int64).reshape(-1))
+    if len(reps_h) != r.B or (reps_h < 0).any():
+        raise ValueError("reps must have one non-negative entry per utterance")
+    lengths = r.lengths_host * reps_h
+    starts, total = _aligned_starts(lengths)
+    out = torch.zeros(max(total, ALIGN), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        reps_d, starts_d = torch.from_numpy(reps_h).to(dev), torch.from_numpy(starts).to(dev)
+        nv.check(nv.lib.lidbox_signal_tile(nv.ptr(r.flat), nv.ptr(r.starts), nv.ptr(r.lengths), nv.ptr(reps_d), nv.ptr(out),
+                                           nv.ptr(starts_d), r.B, int(lengths.max()) if r.B else 0, nv.current_stream()))
+    return RaggedSignals(out, starts, lengths)
+
+
+def input_chunk_counts(num_frames, length, step):
+    """tf.signal.frame(x, length, step, axis=0) without padding (steps.py:567): max(0, 1 + (T - length) // step) windows"""
+    length, step = int(length), int(step)
+    if length < 1 or step < 1:
+        raise ValueError("chunk length and step must be at least one frame")
+    t = np.asarray(num_frames, np.int64)
+    return np.maximum(0, 1 + (t - length) // step).astype(np.int64)
+
+
+def input_chunks(inputs, length, step):
+    """steps.py:567 for a list of [T_b, C] device tensors with one C: windows of `length` frames every `step` frames ->
+    (chunks [total, length, C] dense, chunks per element).  A [T, C] matrix flattened is a signal of T * C samples and a
+    window is lidbox_signal_chunks with L = length * C, S = step * C; only whole windows are planned, so nothing is padded."""
+    xs = [nv.require_gpu_tensor(x, "input", torch.float32) for x in inputs]
+    if any(x.dim() != 2 for x in xs) or len({int(x.shape[1]) for x in xs}) > 1:
+        raise ValueError("inputs must be [T, C] matrices with the same number of channels")
+    nch = input_chunk_counts([int(x.shape[0]) for x in xs], length, step)
+    if not xs:
+        return torch.zeros((0, int(length), 0), dtype=torch.float32, device=_device()), nch
+    C = int(xs[0].shape[1])
+    dev = xs[0].device
+    L, S = int(length) * C, int(step) * C
+    if L > 2 ** 31 - 1 or S > 2 ** 31 - 1:
+        raise ValueError("length * C = %d or step * C = %d does not fit a 32-bit chunk size" % (L, S))
+    total = int(nch.sum())
+    out = torch.empty((total, int(length), C), dtype=torch.float32, device=dev)
+    if total and C:
+        r = RaggedSignals.from_list([x.reshape(-1) for x in xs], device=dev)
+        _, co_d = _csr(nch, dev)
+        with torch.cuda.device(dev):
+            nv.check(nv.lib.lidbox_signal_chunks(nv.ptr(r.flat), nv.ptr(r.starts), nv.ptr(r.lengths), nv.ptr(co_d), r.B,
+                                                 total, L, S, nv.ptr(out), nv.current_stream()))
+    return out, nch
