@@ -392,9 +392,11 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restri
     const int d = blockIdx.x * 256 + threadIdx.x;
     if (d >= D) return;
     const int64_t r0 = seg[s], r1 = seg[s + 1];
-    float acc = 0.f;
-    for (int64_t r = r0; r < r1; ++r) acc += x[r * D + d];
-    out[(int64_t)s * D + d] = acc / (float)(r1 - r0);
+    // float64 running sum: a segment may hold thousands of rows, and a sequential fp32 sum loses about sqrt(rows) ulps
+    // of the mean on data with an offset; in float64 the result is the correctly rounded mean to within one fp32 ulp
+    double acc = 0.0;
+    for (int64_t r = r0; r < r1; ++r) acc += (double)x[r * D + d];
+    out[(int64_t)s * D + d] = (float)(acc / (double)(r1 - r0));
 }
 
 // ---- 16-bit PCM ingest: out[f] = mean over channels of pcm[f][c] / 32768  (features/audio.py:17-23) ----

@@ -142,3 +142,92 @@ def numpy_snr_mixer_reference_twin(clean, noise, snr):
     noisescalar = np.sqrt(rmsclean / (10 ** (snr / 20)) / rmsnoise)
     noisenewlevel = noise * noisescalar
     return clean, noisenewlevel, clean + noisenewlevel
+
+
+# --------------------------------------------------------------------------- planted VAD inputs
+# Inputs whose VAD answer is known by construction (tests/test_oracle_signal.py proves it on the CPU,
+# tests/test_signal_paths_gpu.py holds the kernels to it bit for bit).
+
+VAD_PLAN_MIN_LENS = (1, 2, 3, 30, 100)
+VAD_PLAN_FRAME_LENS = (160, 400, 7, 6, 1)
+VAD_PLAN_SIZES = (0, 1, 255, 256, 257, 1000, 60000)          # frames; the last is ten minutes of 10 ms frames
+
+
+def vad_run_lengths(min_len):
+    """the non-speech run lengths on either side of the inversion rule: min_len - 1, min_len, min_len + 1, 2 min_len + 5"""
+    return [n for n in (min_len - 1, min_len, min_len + 1, 2 * min_len + 5) if n > 0]
+
+
+def invert_too_short_brute_force(mask, min_length):
+    """the definition of invert_too_short_consecutive_false, frame by frame: a frame is inverted iff it is False and its
+    maximal run of False is shorter than min_length"""
+    mask = [bool(v) for v in mask]
+    out = list(mask)
+    for i, v in enumerate(mask):
+        if v:
+            continue
+        a = i
+        while a > 0 and not mask[a - 1]:
+            a -= 1
+        b = i
+        while b + 1 < len(mask) and not mask[b + 1]:
+            b += 1
+        if b - a + 1 < min_length:
+            out[i] = True
+    return np.array(out, bool)
+
+
+def vad_frame_plans(min_len, seed=0):
+    """per-utterance boolean plans (True = loud frame) for one min_len, in batch order:
+      * runs of vad_run_lengths(min_len) quiet frames at the start, in the middle and at the end of an utterance;
+      * two neighbours that end / start with min_len - 1 quiet frames (both runs inverted, never merged);
+      * quiet runs that straddle a multiple of 256 of the batch's global frame index;
+      * utterances of VAD_PLAN_SIZES frames with random runs of 1 .. 2 min_len + 5 frames."""
+    rng = np.random.default_rng(1000 + 7 * min_len + seed)
+    T, F = np.ones, np.zeros
+    plans = []
+    for n in vad_run_lengths(min_len):
+        plans.append(np.concatenate([F(n, bool), T(min_len + 3, bool)]))                           # start
+        plans.append(np.concatenate([T(5, bool), F(n, bool), T(2 * min_len + 1, bool)]))           # middle
+        plans.append(np.concatenate([T(min_len + 2, bool), F(n, bool)]))                           # end
+    if min_len >= 2:
+        plans.append(np.concatenate([T(4, bool), F(min_len - 1, bool)]))
+        plans.append(np.concatenate([F(min_len - 1, bool), T(4, bool)]))
+    for n in sorted({max(2, min_len - 1), max(2, min_len), 2 * min_len + 5}):
+        done = sum(len(p) for p in plans)
+        lead = (-(done + 3)) % 256 + 3 - n // 2                 # the run covers global frames k * 256 - n // 2 .. + n
+        if lead < 1:
+            lead += 256
+        plans.append(np.concatenate([T(lead, bool), F(n, bool), T(3, bool)]))
+        first = done + lead
+        assert first // 256 != (first + n - 1) // 256
+    for size in VAD_PLAN_SIZES:
+        p = np.zeros(size, bool)
+        i, loud = 0, bool(rng.integers(0, 2))
+        while i < size:
+            n = int(rng.integers(1, 2 * min_len + 6)) if rng.random() < 0.7 else int(rng.choice(vad_run_lengths(min_len)))
+            p[i:i + n] = loud
+            i, loud = i + n, not loud
+        plans.append(p)
+    plans.append(np.zeros(2 * min_len + 7, bool))               # all quiet: stays non-speech
+    return plans
+
+
+def planted_vad_signal(plan, frame_len, tail, rng):
+    """float32 signal of len(plan) frames + `tail` (< frame_len) more samples: noise of amplitude 0.2 (every |sample| in
+    [0.1, 0.2], so even a one-sample frame is loud), quiet frames are the same noise scaled by 1e-4"""
+    n = len(plan) * frame_len
+    u = rng.random(n + tail, dtype=np.float32) - np.float32(0.5)
+    x = np.copysign(np.float32(0.1) + np.float32(0.2) * np.abs(u), u).astype(np.float32)
+    if n:
+        scale = np.where(plan, np.float32(1.0), np.float32(1e-4)).astype(np.float32)
+        x[:n] = (x[:n].reshape(len(plan), frame_len) * scale[:, None]).reshape(-1)
+    return x
+
+
+def planted_vad_batch(min_len, frame_len, seed=0):
+    """-> (plans, signals) of one test case"""
+    plans = vad_frame_plans(min_len, seed)
+    rng = np.random.default_rng(77 * frame_len + min_len + seed)
+    sigs = [planted_vad_signal(p, frame_len, (3 * b) % frame_len, rng) for b, p in enumerate(plans)]
+    return plans, sigs

@@ -107,3 +107,70 @@ def test_snr_mixer_matches_reference_numpy_twin(snr):
         assert np.abs(x - y).max() < 1e-12
     # the mixture has the requested SNR in the reference's (amplitude-ratio under a square root) sense
     assert abs(so.root_mean_square(a[0]) - 10 ** (-25 / 20)) < 1e-12
+
+
+@pytest.mark.parametrize("min_len", so.VAD_PLAN_MIN_LENS)
+def test_invert_too_short_matches_brute_force_definition(min_len):
+    """a frame is inverted iff it is False and its maximal run of False is shorter than min_len -- frame by frame, at run
+    lengths min_len - 1, min_len, min_len + 1 and 2 min_len + 5 at the start, middle and end, and on random masks"""
+    rng = np.random.default_rng(min_len)
+    masks = [p for p in so.vad_frame_plans(min_len) if len(p) <= 1000]
+    assert any(len(p) == 0 for p in masks) and any(len(p) == 1 for p in masks)
+    for n in so.vad_run_lengths(min_len):
+        for lead, trail in ((0, 0), (0, 2), (2, 0), (1, 1)):
+            masks.append(np.concatenate([np.ones(lead, bool), np.zeros(n, bool), np.ones(trail, bool)]))
+    masks += [rng.random(int(rng.integers(1, 400))) < rng.random() for _ in range(20)]
+    for m in masks:
+        got = so.invert_too_short_consecutive_false(m, min_len)
+        ref = so.invert_too_short_brute_force(m, min_len)
+        assert got.dtype == bool and got.shape == ref.shape and (got == ref).all()
+    # the planted lengths fall on the side of the rule they were chosen for
+    for n in so.vad_run_lengths(min_len):
+        m = np.concatenate([np.ones(2, bool), np.zeros(n, bool), np.ones(2, bool)])
+        assert so.invert_too_short_consecutive_false(m, min_len)[2:2 + n].all() == (n < min_len)
+
+
+def test_planted_vad_plans_hold_the_cases_they_claim():
+    for min_len in so.VAD_PLAN_MIN_LENS:
+        plans = so.vad_frame_plans(min_len)
+        sizes = [len(p) for p in plans]
+        assert all(s in sizes for s in so.VAD_PLAN_SIZES)
+        off = np.concatenate(([0], np.cumsum(sizes)))
+        straddles, pairs = 0, 0
+        for b, p in enumerate(plans):
+            pos, lengths = so.run_length_encoding(p.astype(np.int32))
+            for a, n in zip(pos, lengths):
+                if not p[a] and (off[b] + a) // 256 != (off[b] + a + n - 1) // 256:
+                    straddles += 1
+            if b and min_len >= 2 and len(p) > min_len and len(plans[b - 1]) > min_len:
+                prev = plans[b - 1]
+                if (not prev[-(min_len - 1):].any() and prev[-min_len] and not p[:min_len - 1].any() and p[min_len - 1]):
+                    pairs += 1
+                    k = min_len - 1
+                    assert so.invert_too_short_consecutive_false(prev, min_len)[-k:].all()
+                    assert so.invert_too_short_consecutive_false(p, min_len)[:k].all()
+                    merged = so.invert_too_short_consecutive_false(np.concatenate([prev, p]), min_len)
+                    assert not merged[len(prev) - k:len(prev) + k].any()       # what a kernel that ignored the boundary would give
+        assert straddles >= 3 and (pairs >= 1 or min_len < 2)
+        # both outcomes of the rule are present at this min_len (the parent's cases never kept a run with min_len > 5)
+        kept = sum(int((~so.invert_too_short_consecutive_false(p, min_len)).sum()) for p in plans)
+        flipped = sum(int((so.invert_too_short_consecutive_false(p, min_len) & ~p).sum()) for p in plans)
+        assert kept > 0 and (flipped > 0 or min_len == 1)
+
+
+@pytest.mark.parametrize("frame_len", so.VAD_PLAN_FRAME_LENS)
+@pytest.mark.parametrize("min_len", so.VAD_PLAN_MIN_LENS)
+def test_planted_vad_inputs_are_decided_with_margin(min_len, frame_len):
+    """the input condition of the exact GPU test: in float64 every frame RMS is further than 1e-3 * threshold from the
+    utterance's threshold and `rms > threshold` is the plan, so an fp32 and an fp64 comparison cannot disagree"""
+    plans, sigs = so.planted_vad_batch(min_len, frame_len)
+    for strength in (0.05, 0.5):
+        for p, s in zip(plans, sigs):
+            frames = so.frame_nonoverlapping(s.astype(np.float64), frame_len)
+            assert len(frames) == len(p) and len(s) - len(p) * frame_len < frame_len
+            if not len(p):
+                continue
+            rms = so.root_mean_square(frames, axis=1)
+            thr = strength * max(1e-3, rms.mean())
+            assert (np.abs(rms - thr) > 1e-3 * thr).all()
+            assert ((rms > thr) == p).all()

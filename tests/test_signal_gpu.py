@@ -46,6 +46,7 @@ def test_vad_decisions_and_apply_match_oracle(frame_len, min_frames, strength):
     vad = sg.vad_decisions(r, frame_len, min_frames, strength)
     got = [d.cpu().numpy().astype(bool) for d in sg.split_frames(vad, vad["decisions"])]
     rms = [x.cpu().numpy() for x in sg.split_frames(vad, vad["rms"])]
+    thr_gpu = vad["thresholds"].cpu().numpy()
     voiced = sg.apply_vad(r, vad)
     out = [v.cpu().numpy() for v in voiced.split()]
     for b, s in enumerate(sigs):
@@ -56,11 +57,14 @@ def test_vad_decisions_and_apply_match_oracle(frame_len, min_frames, strength):
             assert np.abs(rms[b] - ref_rms).max() <= 1e-5 * max(1e-12, ref_rms.max())
             thr = strength * max(1e-3, ref_rms.mean())
             ref = so.invert_too_short_consecutive_false(ref_rms > thr, min_frames)
+            assert abs(thr_gpu[b] - thr) <= 1e-5 * thr, b
+            # exact for every utterance: the inversion rule applied to the kernel's own comparison
+            assert (got[b] == so.invert_too_short_consecutive_false(rms[b] > thr_gpu[b], min_frames)).all(), b
             safe = np.abs(ref_rms - thr) > 1e-5 * thr      # frames whose fp32 / fp64 comparison cannot differ
             if safe.all():
                 assert (got[b] == ref).all(), b
-            else:
-                assert (got[b][safe] == (ref_rms > thr)[safe]).all() or min_frames > 0
+            elif min_frames == 0:
+                assert (got[b][safe] == (ref_rms > thr)[safe]).all(), b
         # applying the kernel's own decisions gathers exactly those frames, in order
         ref_out = frames[got[b]].reshape(-1).astype(np.float32) if len(frames) else np.zeros(0, np.float32)
         assert out[b].shape == ref_out.shape and (out[b] == ref_out).all(), b
