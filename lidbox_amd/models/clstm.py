@@ -16,8 +16,8 @@ sequence frame4 reads in place.  The images are stored time-major, [B][T][F][C],
 Reshape((T, F, 1)) with height = time.  Front-end per layer: lidbox_conv2d_strided_fwd (fp32 MFMA, taps that lie wholly in the
 padding skipped) -> lidbox_bn_train_stats (4-D input: tf.keras' fused path, Bessel-corrected moving variance) ->
 lidbox_bn_relu_fwd / lidbox_bn_relu_maxf_fwd; backward lidbox_bn_relu_maxf_bwd (TF's even split over ties) / lidbox_bn_relu_bwd
--> lidbox_bn_bwd -> lidbox_conv2d_strided_wgrad, and lidbox_conv2d_strided_dgrad for conv2d_2.  The LSTM is the stepped
-lidbox_lstm_fwd / _bwd walk with its projection and weight gradients on the GEMM family (models/rnn.py's scheme).
+-> lidbox_bn_bwd -> lidbox_conv2d_strided_wgrad, and lidbox_conv2d_strided_dgrad for conv2d_2.  The LSTM is models/flat.py's
+lstm_layer_fwd / lstm_layer_bwd on the lidbox_lstm_fwd / _bwd walk, with its GEMMs on the model's GEMM family.
 
 Input noise and channel dropout run as ONE launch (lidbox_input_noise_dropout) keyed by the Trainer's device step counter,
 so every replay of the captured step draws fresh noise; outside training neither is applied.
@@ -28,14 +28,13 @@ correct: every bucket boundary is a frame layer's kernel, and each parameter's g
 completes its bucket ends.  BatchNormalization moving statistics live in `state`.  fp32 only.
 """
 import ctypes
-import math
 
 import numpy as np
 import torch
 
 from .. import _native as nv
-from .rnn import orthogonal
-from .tdnn import DenseSpec, FreqAttentionSpec, SequentialTDNN, _align4, _rows
+from .flat import BatchNormSpec, FlatParams, LSTMLayer, _rows, lstm_layer_bwd, lstm_layer_fwd
+from .tdnn import DenseSpec, FreqAttentionSpec, SequentialTDNN, _Workspace as _TDNNWorkspace
 from .xvector import frame_layer, segment_layer
 
 NOISE_STDDEV = 0.01                 # clstm.py:48
@@ -126,8 +125,20 @@ def _check_args(input_shape, compute_dtype, use_attention, use_conv2d, filters, 
         raise ValueError("conv2d filters must be multiples of 16, got %r" % (tuple(filters),))
 
 
+class _Workspace(_TDNNWorkspace):
+    """SequentialTDNN's buffers plus those of the 2-D front-end and the LSTM"""
+
+    def __init__(self, model, B, T):
+        super().__init__(model, B, T)
+        model._extend_workspace(self)
+
+
 class CLSTM(SequentialTDNN):
     """The reference's CLSTM on SequentialTDNN (see the module docstring)."""
+
+    workspace_class = _Workspace
+    unit_forget_biases = frozenset(["lstm.b"])
+    _init_weights = FlatParams._init_weights          # the Keras defaults of every layer kind, not just SequentialTDNN's
 
     def __init__(self, input_shape, num_outputs, output_activation="log_softmax", use_attention=False, use_conv2d=False,
                  use_lstm=False, seed=None, device=None, compute_dtype="float32", filters=FILTERS, frame_units=FRAME_UNITS,
@@ -148,55 +159,15 @@ class CLSTM(SequentialTDNN):
         self.model_input_dim = F
         self.input_noise_stddev = NOISE_STDDEV          # the Trainer's cue for lidbox_input_noise_dropout
         # the Keras layout in the bucket-safe order (module docstring) replaces the plain x-vector one
-        self.layout, self.state_layout = {}, {}
-        off = soff = 0
+        self.new_layout()
         for name, shape, trainable in keras_layout(input_shape, num_outputs, use_attention, use_conv2d, use_lstm, filters,
                                                    frame_units, segment_units):
-            n = int(np.prod(shape))
-            if trainable:
-                self.layout[name] = (off, shape)
-                off = _align4(off + n)
-            else:
-                self.state_layout[name] = (soff, shape)
-                soff = _align4(soff + n)
-        self.num_flat = off
-        self.flat = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.flat_grad = torch.zeros_like(self.flat)
-        self.state = torch.zeros(max(soff, 4), dtype=torch.float32, device=self.device)
+            (self.add_param if trainable else self.add_state)(name, shape)
+        self.allocate()
         self._init_weights(seed)
-
-    # ------------------------------------------------------------------ parameters
-    def _init_weights(self, seed):
-        """Keras defaults: glorot_uniform kernels (Conv2D fan = kt kf C), orthogonal recurrent kernel, zero biases with the
-        LSTM forget gate's quarter at 1, gamma 1, beta 0, moving mean 0, moving variance 1"""
-        rng = np.random.default_rng(seed)
-        host = np.zeros(self.num_flat, np.float32)
-        for name, (off, shape) in self.layout.items():
-            n = int(np.prod(shape))
-            if name.endswith(".U"):
-                host[off:off + n] = orthogonal(shape, rng).astype(np.float32).ravel()
-            elif name.endswith(".W"):
-                rf = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
-                limit = math.sqrt(6.0 / (rf * shape[-2] + rf * shape[-1]))
-                host[off:off + n] = rng.uniform(-limit, limit, size=n).astype(np.float32)
-            elif name.endswith(".gamma"):
-                host[off:off + n] = 1.0
-            elif name == "lstm.b":
-                H = shape[0] // 4
-                host[off + H:off + 2 * H] = 1.0
-        self.flat.copy_(torch.from_numpy(host))
-        self.state.zero_()
-        for name, (off, shape) in self.state_layout.items():
-            if name.endswith(".moving_variance"):
-                self.state[off:off + shape[0]] = 1.0
+        self.fe_bns = [BatchNormSpec("conv2d_%d_bn" % l, BN_MOMENTUM, BN_EPSILON) for l in (1, 2)]
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T):
-        ws = super().workspace(B, T)
-        if not hasattr(ws, "cl_gemm_ws"):
-            self._extend_workspace(ws)
-        return ws
-
     def _extend_workspace(self, ws):
         dev, B, T = self.device, ws.B, ws.T
         f32 = dict(dtype=torch.float32, device=dev)
@@ -213,8 +184,8 @@ class CLSTM(SequentialTDNN):
             ws.cv_dbn = [torch.zeros_like(y) for y in ws.cv_y]  # gradient of each BatchNormalization output
             ws.cv_dz = [torch.zeros_like(y) for y in ws.cv_y]   # gradient of each conv output
             R1, R2 = B * T * F1, B * T * F2
-            ws.cv_bn_ws = torch.empty(max(16, nv.lib.lidbox_bn_workspace(max(R1, 1), C1), nv.lib.lidbox_bn_workspace(max(R2, 1), C2)),
-                                      dtype=torch.uint8, device=dev)
+            ws.bn_ws = torch.empty(max(16, nv.lib.lidbox_bn_workspace(max(R1, 1), C1), nv.lib.lidbox_bn_workspace(max(R2, 1), C2)),
+                                   dtype=torch.uint8, device=dev)
             ws.cv_dgrad_ws = torch.empty(max(16, nv.lib.lidbox_conv2d_strided_dgrad_workspace(tp2, C1, C2)), dtype=torch.uint8, device=dev)
             wws = 16
             if B > 0:
@@ -240,13 +211,18 @@ class CLSTM(SequentialTDNN):
     def _cws(self, ws):
         return nv.ptr(ws.cl_gemm_ws), ws.cl_gemm_ws.numel()
 
+    def _lstm(self, ws):
+        T3, H, C3 = ws.Ts[3], self.lstm_units, self.convs[2].filters
+        return LSTMLayer(["lstm"], _rows(ws.act[3].data_ptr(), 0, C3, 1, ws.B * T3), C3, ws.B, T3, H, ws.lstm_zg, ws.lstm_cseq,
+                         ws.lstm_hseq.data_ptr(), H, ws.lstm_ws, ws.cl_gemm_ws, ws.cl_gemm_ws, gemm=self.gemm)
+
     def _conv_rows_in(self, ws, i):
         if i == 3 and self.use_lstm:        # frame4 (k 1, s 1) reads the LSTM's h sequence in place
             H, T3 = self.lstm_units, ws.Ts[3]
             return _rows(ws.lstm_hseq.data_ptr() + 4 * H, (T3 + 2) * H, H, ws.B, ws.Ts[4])
         return super()._conv_rows_in(ws, i)
 
-    def _sp4(self, c, C):
+    def _const_ptrs(self, c, C):
         return [ctypes.c_void_p(c.data_ptr() + 4 * j * C) for j in range(4)]
 
     # ------------------------------------------------------------------ forward
@@ -264,19 +240,10 @@ class CLSTM(SequentialTDNN):
         x, cin = ws.fe_in, 1
         for l, (Fi, Fo, taps) in enumerate(self.fe_geom):
             name, C = "conv2d_%d" % (l + 1), self.filters[l]
-            bn, y, R = name + "_bn", ws.cv_y[l], B * T * Fo
+            y, R = ws.cv_y[l], B * T * Fo
             nv.check(lib.lidbox_conv2d_strided_fwd(nv.ptr(x), B, T, Fi, cin, self._p(name + ".W"), taps, C, self._p(name + ".b"),
                                                    nv.ptr(y), st))
-            cp = self._sp4(ws.cv_c[l], C)
-            if training:
-                mm = self._sp(bn + ".moving_mean") if update_moving else None
-                mv = self._sp(bn + ".moving_variance") if update_moving else None
-                nv.check(lib.lidbox_bn_train_stats(nv.ptr(y), R, C, self._p(bn + ".gamma"), self._p(bn + ".beta"), BN_EPSILON,
-                                                   BN_MOMENTUM, mm, mv, cp[0], cp[1], cp[2], cp[3], nv.ptr(ws.cv_bn_ws),
-                                                   ws.cv_bn_ws.numel(), st))
-            else:
-                nv.check(lib.lidbox_bn_infer_consts(self._p(bn + ".gamma"), self._p(bn + ".beta"), self._sp(bn + ".moving_mean"),
-                                                    self._sp(bn + ".moving_variance"), BN_EPSILON, C, cp[2], cp[3], st))
+            cp = self._bn_fwd(self.fe_bns[l], y, R, C, ws.cv_c[l], None, ws, training, update_moving, bessel=None)
             if l == 0:
                 nv.check(lib.lidbox_bn_relu_fwd(nv.ptr(y), R, C, cp[2], cp[3], nv.ptr(ws.cv_a1), st))
                 x, cin = ws.cv_a1, C
@@ -287,17 +254,8 @@ class CLSTM(SequentialTDNN):
                                                      ctypes.c_void_p(a0.data_ptr() + 4 * ws.pads[0] * C), a0.shape[1] * C, st))
 
     def _forward_lstm(self, ws):
-        st, lib = nv.current_stream(), nv.lib
-        B, T3, H = ws.B, ws.Ts[3], self.lstm_units
-        if B * T3 == 0:
-            return
-        C3 = self.convs[2].filters
-        gws, gws_n = self._cws(ws)
-        X = _rows(ws.act[3].data_ptr(), 0, C3, 1, B * T3)
-        nv.check(self.gemm.nn(X, self._p("lstm.W"), 4 * H, _rows(ws.lstm_zg.data_ptr(), 0, 4 * H, 1, B * T3), C3, 4 * H,
-                              nv.EPI_BIAS, self._p("lstm.b"), gws, gws_n, st))
-        nv.check(lib.lidbox_lstm_fwd(self._p("lstm.U"), None, 1, B, T3, H, nv.ptr(ws.lstm_zg), nv.ptr(ws.lstm_hseq),
-                                     nv.ptr(ws.lstm_cseq), nv.ptr(ws.lstm_ws), ws.lstm_ws.numel(), st))
+        if ws.B * ws.Ts[3] > 0:
+            lstm_layer_fwd(self, self._lstm(ws))
 
     # ------------------------------------------------------------------ backward
     def backward_conv_ws(self, ws, i):
@@ -315,8 +273,7 @@ class CLSTM(SequentialTDNN):
     def _backward_frame4_lstm(self, ws):
         """frame4's wgrad and its dgrad into the h sequence's gradient (no ReLU in between), then the LSTM: the walk back,
         dW with db, dU, and dX into dact[3] masked by frame3's ReLU"""
-        st, lib = nv.current_stream(), nv.lib
-        B, T3, H = ws.B, ws.Ts[3], self.lstm_units
+        T3, H = ws.Ts[3], self.lstm_units
         c, C3, R = self.convs[3], self.convs[2].filters, ws.B * ws.Ts[3]
         if R == 0:
             self._zero_grads("frame4.W", "frame4.b", "lstm.W", "lstm.U", "lstm.b")
@@ -325,16 +282,8 @@ class CLSTM(SequentialTDNN):
         self._dgrad_wgrad(ws, dy, self._p(c.name + ".W"), c.filters, _rows(ws.lstm_dh.data_ptr(), 0, H, 1, R), c.filters, H,
                           nv.EPI_NONE, None, self._conv_rows_in(ws, 3), self._p(c.name + ".W", True), c.filters, H,
                           self._p(c.name + ".b", True))
-        nv.check(lib.lidbox_lstm_bwd(self._p("lstm.U"), None, 1, B, T3, H, nv.ptr(ws.lstm_zg), nv.ptr(ws.lstm_cseq),
-                                     nv.ptr(ws.lstm_dh), T3 * H, None, nv.ptr(ws.lstm_ws), ws.lstm_ws.numel(), st))
-        gws, gws_n = self._cws(ws)
-        dz = _rows(ws.lstm_zg.data_ptr(), 0, 4 * H, 1, R)
-        X = _rows(ws.act[3].data_ptr(), 0, C3, 1, R)
-        nv.check(self.gemm.tn(X, dz, self._p("lstm.W", True), 4 * H, C3, 4 * H, 0, self._p("lstm.b", True), gws, gws_n, st))
-        hprev = _rows(ws.lstm_hseq.data_ptr(), (T3 + 2) * H, H, B, T3)          # h_{t-1}: row 0 is the zero state
-        nv.check(self.gemm.tn(hprev, dz, self._p("lstm.U", True), 4 * H, H, 4 * H, 0, None, gws, gws_n, st))
-        nv.check(self.gemm.nt(dz, self._p("lstm.W"), 4 * H, _rows(ws.dact[3].data_ptr(), 0, C3, 1, R), 4 * H, C3,
-                              nv.EPI_RELU_MASK if self.convs[2].relu else nv.EPI_NONE, nv.ptr(ws.act[3]), gws, gws_n, st))
+        lstm_layer_bwd(self, self._lstm(ws), nv.ptr(ws.lstm_dh), T3 * H, H, dX=_rows(ws.dact[3].data_ptr(), 0, C3, 1, R),
+                       dX_epi=(nv.EPI_RELU_MASK if self.convs[2].relu else nv.EPI_NONE,), dX_aux=nv.ptr(ws.act[3]))
 
     def _backward_conv2d(self, ws):
         """frame1's dgrad into the front-end output's gradient, then both Conv2D layers from the top down"""
@@ -356,24 +305,19 @@ class CLSTM(SequentialTDNN):
                                   nv.EPI_NONE if j == 0 else nv.EPI_ACCUM, None, gws, gws_n, st))
         (F0, F1, tp1), (_, F2, tp2) = self.fe_geom
         C1 = self.filters[0]
-        (n1, bn1), (n2, bn2) = names
-        c1, c2 = self._sp4(ws.cv_c[0], C1), self._sp4(ws.cv_c[1], C2)
-        bws, bws_n = nv.ptr(ws.cv_bn_ws), ws.cv_bn_ws.numel()
+        (n1, _), (n2, _) = names
+        c1, c2 = self._const_ptrs(ws.cv_c[0], C1), self._const_ptrs(ws.cv_c[1], C2)
         R1, R2 = B * T * F1, B * T * F2
         nv.check(lib.lidbox_bn_relu_maxf_bwd(nv.ptr(ws.cv_y[1]), B, T, F2, C2, c2[2], c2[3],
                                              ctypes.c_void_p(d0.data_ptr() + 4 * ws.pads[0] * C2), Tp * C2, nv.ptr(ws.cv_dbn[1]), st))
-        nv.check(lib.lidbox_bn_bwd(nv.ptr(ws.cv_y[1]), _rows(ws.cv_dbn[1].data_ptr(), 0, C2, 1, R2), R2, C2, c2[0], c2[1],
-                                   self._p(bn2 + ".gamma"), 0, self._p(bn2 + ".gamma", True), self._p(bn2 + ".beta", True),
-                                   nv.ptr(ws.cv_dz[1]), bws, bws_n, st))
+        self._bn_bwd(self.fe_bns[1], ws.cv_y[1], R2, C2, ws.cv_c[1], ws.cv_dbn[1], 0, ws.cv_dz[1], ws)
         wws, wws_n = nv.ptr(ws.cv_wgrad_ws), ws.cv_wgrad_ws.numel()
         nv.check(lib.lidbox_conv2d_strided_wgrad(nv.ptr(ws.cv_a1), nv.ptr(ws.cv_dz[1]), B, T, F1, C1, C2, tp2, self._p(n2 + ".W", True),
                                                  self._p(n2 + ".b", True), wws, wws_n, st))
         nv.check(lib.lidbox_conv2d_strided_dgrad(nv.ptr(ws.cv_dz[1]), B, T, F1, C1, C2, self._p(n2 + ".W"), tp2, nv.ptr(ws.cv_dbn[0]),
                                                  nv.ptr(ws.cv_dgrad_ws), ws.cv_dgrad_ws.numel(), st))
         nv.check(lib.lidbox_bn_relu_bwd(nv.ptr(ws.cv_y[0]), R1, C1, c1[2], c1[3], nv.ptr(ws.cv_dbn[0]), nv.ptr(ws.cv_dbn[0]), st))
-        nv.check(lib.lidbox_bn_bwd(nv.ptr(ws.cv_y[0]), _rows(ws.cv_dbn[0].data_ptr(), 0, C1, 1, R1), R1, C1, c1[0], c1[1],
-                                   self._p(bn1 + ".gamma"), 0, self._p(bn1 + ".gamma", True), self._p(bn1 + ".beta", True),
-                                   nv.ptr(ws.cv_dz[0]), bws, bws_n, st))
+        self._bn_bwd(self.fe_bns[0], ws.cv_y[0], R1, C1, ws.cv_c[0], ws.cv_dbn[0], 0, ws.cv_dz[0], ws)
         nv.check(lib.lidbox_conv2d_strided_wgrad(nv.ptr(ws.fe_in), nv.ptr(ws.cv_dz[0]), B, T, F0, 1, C1, tp1, self._p(n1 + ".W", True),
                                                  self._p(n1 + ".b", True), wws, wws_n, st))
 

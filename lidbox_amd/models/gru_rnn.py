@@ -5,8 +5,7 @@ A model is  [SpatialDropout1D]  ->  GRU / Bidirectional(GRU) layers  ->  the las
 concatenated, forward t = T-1 and backward t = 0)  ->  [BatchNormalization]  ->  Dense layers, each optionally followed by
 BatchNormalization  ->  output activation (reference lidbox/models/bi_gru.py:26-48).
 
-Everything numeric is a liblidbox_hip.so call on preallocated device buffers, so `lidbox_amd.train.Trainer` captures the whole
-train step into a hipGraph (one gradient bucket, backward is `backward_head_ws`).  Per GRU layer and direction: the input
+The scaffolding is `lidbox_amd.models.flat`'s.  Per GRU layer and direction: the input
 projection X W + b_in of all B*T rows is one lidbox_gemm_nn; the walk through time is lidbox_gru_fwd / _bwd (csrc/gru.hip, one
 launch per step for both directions); dW = X^T dZx (with db_in), dU = H_prev^T dZrec (with db_rec, in two column blocks:
 dZrec's h block lives in qh) and dX = dZx W^T are GEMMs.
@@ -16,22 +15,18 @@ population variance, move the running variance towards the population variance (
 moving statistics live in `state` / `state_layout` and move only when `update_moving` (not in the Trainer's warm-up pass), as
 in `lidbox_amd.models.xvector_2d`.
 
-Parameters live in one flat fp32 buffer in Keras layouts: kernel W [C, 3H], recurrent_kernel U [H, 3H], bias b [2, 3H]
-(input bias, recurrent bias), gate order z, r, h.  A Bidirectional wrapper's halves are named by wrapper and direction
-(`BGRU_1_forward.W`, `BGRU_1_backward.U`), not by Keras' session-dependent inner names; Dense and BatchNormalization layers
-keep their Keras names (`fc_relu_1.W`, `BGRU_2_bn.gamma`, `BGRU_2_bn.moving_variance`).  Initialisation as Keras:
-glorot_uniform kernels, orthogonal recurrent kernels, zero biases, BatchNormalization gamma 1 / beta 0 / moving mean 0 /
-moving variance 1.
+Keras layouts of a GRU: kernel W [C, 3H], recurrent_kernel U [H, 3H], bias b [2, 3H] (input bias, recurrent bias), gate
+order z, r, h.  A Bidirectional wrapper's halves are named by wrapper and direction (`BGRU_1_forward.W`, `BGRU_1_backward.U`),
+not by Keras' session-dependent inner names; Dense and BatchNormalization layers keep their Keras names (`fc_relu_1.W`,
+`BGRU_2_bn.gamma`, `BGRU_2_bn.moving_variance`).
 """
 import ctypes
-import math
 
-import numpy as np
 import torch
 
 from .. import _native as nv
-from .rnn import RecurrentModel, orthogonal
-from .tdnn import DenseSpec, _rows
+from .flat import BatchNormSpec, FlatModel, Workspace, _rows, h_neighbour_rows
+from .tdnn import DenseSpec
 
 
 class GRUSpec:
@@ -49,18 +44,7 @@ class GRUSpec:
         return self.dirs * self.units
 
 
-class BatchNormSpec:
-    """tf.keras.layers.BatchNormalization defaults on a [B, C] input"""
-
-    def __init__(self, name, momentum=0.99, epsilon=1e-3):
-        self.name, self.momentum, self.epsilon = name, float(momentum), float(epsilon)
-
-
-def _align4(n):
-    return (n + 3) & ~3
-
-
-class _Workspace:
+class _Workspace(Workspace):
     """All per-(B, T) device buffers of one GRU model."""
 
     def __init__(self, model, B, T):
@@ -118,24 +102,16 @@ class _Workspace:
         self.bn_ws = torch.empty(bws, dtype=torch.uint8, device=dev)
         self.pending = []
 
-    def input_view(self):
-        return self.x
 
-    def input_target(self):
-        """(pointer, floats between utterances, T, C) of the model input buffer (what Trainer / _load_input fill)"""
-        return ctypes.c_void_p(self.x.data_ptr()), self.x.stride(0), self.x.shape[1], self.x.shape[2]
+class GRUModel(FlatModel):
+    """[SpatialDropout1D] -> GRU layers -> final state -> [BatchNormalization] -> Dense [+ BatchNormalization] layers (see the
+    module docstring)."""
 
-
-class GRUModel(RecurrentModel):
-    """[SpatialDropout1D] -> GRU layers -> final state -> [BatchNormalization] -> Dense [+ BatchNormalization] layers.
-    Shares the public calls of `RecurrentModel` (workspace cache, input loading, __call__); see the module docstring."""
+    workspace_class = _Workspace
 
     def __init__(self, input_shape, grus, denses, rnn_bn=None, dense_bns=None, name="gru", output_activation="log_softmax",
                  channel_dropout_rate=0.0, seed=None, device=None, compute_dtype="float32"):
-        if compute_dtype not in ("float32", "fp32", "f32", torch.float32):
-            raise ValueError("recurrent models compute in float32 only, got compute_dtype=%r" % (compute_dtype,))
-        if output_activation not in (None, "log_softmax", "softmax"):
-            raise ValueError("output_activation must be None, 'log_softmax' or 'softmax', got %r" % (output_activation,))
+        super().__init__(input_shape, name, output_activation, seed, device, compute_dtype, channel_dropout_rate)
         self.grus, self.denses = list(grus), list(denses)
         if not self.denses or self.grus[-1].return_sequences or not all(l.return_sequences for l in self.grus[:-1]):
             raise ValueError("the last GRU returns its final state only, into Dense layers; the others return sequences")
@@ -143,113 +119,29 @@ class GRUModel(RecurrentModel):
         if len(self.dense_bns) != len(self.denses) or self.dense_bns[-1] is not None:
             raise ValueError("dense_bns: one entry (BatchNormSpec or None) per Dense layer, None for the output layer")
         self.rnn_bn = rnn_bn
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.name = name
-        self.input_shape = tuple(input_shape)
-        self.input_dim = self.model_input_dim = int(input_shape[-1])
-        self.head = "last"
-        self.lstms = []
-        self.output_activation = output_activation
-        self.channel_dropout_rate = float(channel_dropout_rate)
-        self.dropout_seed = int(np.random.default_rng(seed).integers(1, 2 ** 62))
-        self._dropout_calls = 0
-        self.compute_dtype = "float32"
-        # what lidbox_amd.train.Trainer reads from every model
-        self.convs, self.frontend, self.bf16_storage, self.attention = [], None, False, None
-        self.wgrad_stream = None
-        self.head_wgrad_stream = None
-        self.layout, self.state_layout = {}, {}
-        off, soff = 0, 0
-
-        def bn_entries(bn, C):
-            nonlocal off, soff
-            for suffix in (".gamma", ".beta"):
-                self.layout[bn.name + suffix] = (off, (C,))
-                off = _align4(off + C)
-            for suffix in (".moving_mean", ".moving_variance"):
-                self.state_layout[bn.name + suffix] = (soff, (C,))
-                soff = _align4(soff + C)
-
         cin = self.input_dim
         for l in self.grus:
             H = l.units
             for p in l.prefixes:
-                for suffix, shape in ((".W", (cin, 3 * H)), (".U", (H, 3 * H)), (".b", (2, 3 * H))):
-                    self.layout[p + suffix] = (off, shape)
-                    off = _align4(off + int(np.prod(shape)))
+                self.add_param(p + ".W", (cin, 3 * H))
+                self.add_param(p + ".U", (H, 3 * H))
+                self.add_param(p + ".b", (2, 3 * H))
             cin = l.out_dim
         if rnn_bn is not None:
-            bn_entries(rnn_bn, cin)
+            self.add_bn(rnn_bn.name, cin)
         for d, bn in zip(self.denses, self.dense_bns):
-            for suffix, shape in ((".W", (cin, d.units)), (".b", (d.units,))):
-                self.layout[d.name + suffix] = (off, shape)
-                off = _align4(off + int(np.prod(shape)))
+            self.add_param(d.name + ".W", (cin, d.units))
+            self.add_param(d.name + ".b", (d.units,))
             cin = d.units
             if bn is not None:
-                bn_entries(bn, cin)
+                self.add_bn(bn.name, cin)
         self.output_dim = cin
-        self.num_flat = off
-        self.flat = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.flat_grad = torch.zeros_like(self.flat)
-        self.state = torch.zeros(max(soff, 4), dtype=torch.float32, device=self.device)
-        self._init_weights(seed)
-        self._ws = {}
-
-    # ------------------------------------------------------------------ parameters
-    def _init_weights(self, seed):
-        """Keras GRU / Dense / BatchNormalization defaults: glorot_uniform kernels, orthogonal recurrent kernels, zero biases,
-        gamma 1, beta 0, moving mean 0, moving variance 1"""
-        rng = np.random.default_rng(seed)
-        host = np.zeros(self.num_flat, np.float32)
-        for name, (off, shape) in self.layout.items():
-            n = int(np.prod(shape))
-            if name.endswith(".W"):
-                limit = math.sqrt(6.0 / (shape[0] + shape[1]))
-                host[off:off + n] = rng.uniform(-limit, limit, size=n).astype(np.float32)
-            elif name.endswith(".U"):
-                host[off:off + n] = orthogonal(shape, rng).astype(np.float32).ravel()
-            elif name.endswith(".gamma"):
-                host[off:off + n] = 1.0
-        self.flat.copy_(torch.from_numpy(host))
-        self.state.zero_()
-        for name, (off, shape) in self.state_layout.items():
-            if name.endswith(".moving_variance"):
-                self.state[off:off + shape[0]] = 1.0
-
-    def param(self, name, grad=False):
-        if name in self.state_layout:
-            off, shape = self.state_layout[name]
-            return self.state[off:off + int(np.prod(shape))].view(shape)
-        return super().param(name, grad)
-
-    def count_params(self):
-        """Keras `Model.count_params()`: 3H(C + H + 2) per GRU direction, the Dense layers and 4C per BatchNormalization
-        (gamma, beta and the two moving statistics)"""
-        return sum(int(np.prod(s)) for _, s in list(self.layout.values()) + list(self.state_layout.values()))
-
-    def get_weights(self):
-        """dict name -> numpy array in Keras layouts (trainable parameters and the BatchNormalization moving statistics)"""
-        return {n: self.param(n).detach().cpu().numpy().copy() for n in list(self.layout) + list(self.state_layout)}
-
-    def _sp(self, name):
-        off, _ = self.state_layout[name]
-        return ctypes.c_void_p(self.state.data_ptr() + 4 * off)
+        self._finish(seed)
 
     def _b_rec(self, prefix, grad=False):
         """row 1 of the Keras bias [2, 3H]: the recurrent bias"""
         off, shape = self.layout[prefix + ".b"]
         return ctypes.c_void_p((self.flat_grad if grad else self.flat).data_ptr() + 4 * (off + shape[1]))
-
-    # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T):
-        key = (int(B), int(T))
-        ws = self._ws.get(key)
-        if ws is None:
-            if len(self._ws) >= 4:
-                self._ws.pop(next(iter(self._ws)))
-            ws = _Workspace(self, *key)
-            self._ws[key] = ws
-        return ws
 
     def _in_rows(self, ws, i):
         """(rows descriptor, K) of layer i's input: the model input, or rows 1..T of the previous layer's h sequence"""
@@ -263,22 +155,6 @@ class GRUModel(RecurrentModel):
         return self._p(l.prefixes[0] + ".U"), (self._p(l.prefixes[1] + ".U") if l.dirs == 2 else None)
 
     # ------------------------------------------------------------------ forward
-    def _bn_fwd(self, bn, x, C, consts, y, ws, training, update_moving):
-        lib, st = nv.lib, nv.current_stream()
-        B = ws.B
-        cp = [ctypes.c_void_p(consts.data_ptr() + 4 * j * C) for j in range(4)]
-        if training:
-            mm = self._sp(bn.name + ".moving_mean") if update_moving else None
-            mv = self._sp(bn.name + ".moving_variance") if update_moving else None
-            nv.check(lib.lidbox_bn_train_stats_ex(nv.ptr(x), B, C, self._p(bn.name + ".gamma"), self._p(bn.name + ".beta"),
-                                                  bn.epsilon, bn.momentum, 0, mm, mv, cp[0], cp[1], cp[2], cp[3],
-                                                  nv.ptr(ws.bn_ws), ws.bn_ws.numel(), st))
-        else:
-            nv.check(lib.lidbox_bn_infer_consts(self._p(bn.name + ".gamma"), self._p(bn.name + ".beta"),
-                                                self._sp(bn.name + ".moving_mean"), self._sp(bn.name + ".moving_variance"),
-                                                bn.epsilon, C, cp[2], cp[3], st))
-        nv.check(lib.lidbox_bn_apply(nv.ptr(x), B, C, cp[2], cp[3], _rows(y.data_ptr(), 0, C, 1, B), st))
-
     def _head_input(self, ws, j):
         """the input tensor of Dense j"""
         if j == 0:
@@ -309,7 +185,7 @@ class GRUModel(RecurrentModel):
                                         nv.ptr(ws.zg[i]), nv.ptr(ws.hseq[i]), nv.ptr(ws.qh[i]),
                                         nv.ptr(ws.hlast) if last else None, st))
         if self.rnn_bn is not None:
-            self._bn_fwd(self.rnn_bn, ws.hlast, ws.hlast.shape[1], ws.c0, ws.y0, ws, training, update_moving)
+            self._bn_fwd(self.rnn_bn, ws.hlast, B, ws.hlast.shape[1], ws.c0, ws.y0, ws, training, update_moving)
         for j, (d, bn) in enumerate(zip(self.denses, self.dense_bns)):
             x = self._head_input(ws, j)
             din = x.shape[1]
@@ -324,20 +200,10 @@ class GRUModel(RecurrentModel):
                                         d.units, nv.EPI_BIAS_RELU if d.relu else nv.EPI_BIAS, self._p(d.name + ".b"),
                                         gws, gws_n, st))
             if bn is not None:
-                self._bn_fwd(bn, ws.h[j], d.units, ws.c[j], ws.y[j], ws, training, update_moving)
-        if self.output_activation is None:
-            return ws.h[-1]
-        fn = lib.lidbox_softmax_fwd if self.output_activation == "softmax" else lib.lidbox_log_softmax_fwd
-        nv.check(fn(nv.ptr(ws.h[-1]), B, self.output_dim, nv.ptr(ws.logp), st))
-        return ws.logp
+                self._bn_fwd(bn, ws.h[j], B, d.units, ws.c[j], ws.y[j], ws, training, update_moving)
+        return self._output_activation(ws, ws.h[-1], self.output_dim)
 
     # ------------------------------------------------------------------ backward
-    def _bn_bwd(self, bn, x, C, consts, dy, relu_mask, dx, ws):
-        nv.check(nv.lib.lidbox_bn_bwd(nv.ptr(x), _rows(dy.data_ptr(), 0, C, 1, ws.B), ws.B, C, ctypes.c_void_p(consts.data_ptr()),
-                                      ctypes.c_void_p(consts.data_ptr() + 4 * C), self._p(bn.name + ".gamma"), relu_mask,
-                                      self._p(bn.name + ".gamma", True), self._p(bn.name + ".beta", True), nv.ptr(dx),
-                                      nv.ptr(ws.bn_ws), ws.bn_ws.numel(), nv.current_stream()))
-
     def backward_head_ws(self, ws):
         """the whole backward pass (dh[-1] holds d loss / d logits): the Dense / BatchNormalization head, then every GRU
         layer from the top down.  Fills flat_grad (overwrites)."""
@@ -370,10 +236,10 @@ class GRUModel(RecurrentModel):
             if j > 0 and self.dense_bns[j - 1] is not None:
                 # through the BatchNormalization and (relu_mask) the ReLU of Dense j-1: dh[j-1] = d loss / d pre-activation
                 p = self.denses[j - 1]
-                self._bn_bwd(self.dense_bns[j - 1], ws.h[j - 1], p.units, ws.c[j - 1], ws.dy[j - 1], 1 if p.relu else 0,
+                self._bn_bwd(self.dense_bns[j - 1], ws.h[j - 1], B, p.units, ws.c[j - 1], ws.dy[j - 1], 1 if p.relu else 0,
                              ws.dh[j - 1], ws)
         if self.rnn_bn is not None:
-            self._bn_bwd(self.rnn_bn, ws.hlast, ws.hlast.shape[1], ws.c0, ws.dy0, 0, ws.dlast, ws)
+            self._bn_bwd(self.rnn_bn, ws.hlast, B, ws.hlast.shape[1], ws.c0, ws.dy0, 0, ws.dlast, ws)
         for i in range(len(self.grus) - 1, -1, -1):
             l = self.grus[i]
             H, H3, ldo = l.units, 3 * l.units, l.out_dim
@@ -388,8 +254,7 @@ class GRUModel(RecurrentModel):
                 zg, qh = ws.zg[i][d].data_ptr(), ws.qh[i][d].data_ptr()
                 dzx = _rows(zg, 0, H3, 1, B * T)
                 nv.check(lib.lidbox_gemm_tn(X, dzx, self._p(p + ".W", True), H3, K, H3, 0, self._p(p + ".b", True), tws, tws_n, st))
-                prow = 0 if d == 0 else 2                 # h_{t-1} (forward) / h_{t+1} (reverse): zero rows at both ends
-                hprev = _rows(hs + 4 * (prow * ldo + d * H), (T + 2) * ldo, ldo, B, T)
+                hprev = h_neighbour_rows(hs, ldo, d, H, B, T)
                 dU, dbr = self._p(p + ".U", True), self._b_rec(p, True)
                 # dZrec = (dz, dr | dhh * r): its z, r block is dZx's, its h block is qh
                 nv.check(lib.lidbox_gemm_tn(hprev, dzx, dU, H3, H, 2 * H, 0, dbr, tws, tws_n, st))

@@ -7,8 +7,7 @@ K = num_outputs and y_0 = the input [B, T, D], level l = 1..L is
   q = c / sum_t c, att_l = sum_t q * sigmoid(z)  [B, K];
 then Concatenate `attention_concat` of the L attention outputs -> Dense(K) `outputs` -> output activation.
 
-Everything numeric is a liblidbox_hip.so call on preallocated device buffers, so `lidbox_amd.train.Trainer` captures the whole
-train step into a hipGraph (one gradient bucket, backward is `backward_head_ws`).  Every Dense product and weight gradient is
+The scaffolding is `lidbox_amd.models.flat`'s.  Every Dense product and weight gradient is
 one call of the GEMM family over the B*T (or B) rows.  The BatchNormalization apply, the ReLU and the Dropout of a level are
 one pass (lidbox_bn_relu_dropout_fwd / _bwd, csrc/mla.hip), and so is a level's attention pooling
 (lidbox_mla_attention_fwd / _bwd).  The Concatenate is free: the levels write their attention outputs into column slices of one
@@ -23,29 +22,22 @@ Dropout masks are never stored: level l's mask is a counter-based hash of (seed_
 backward.  seed_l is mixed per level and per data-parallel rank as SequentialTDNN._fe_dropout_seed mixes FrameLayer2D's; the
 step is `dropout_step`, which the Trainer points at its optimizer step counter (a standalone training-mode call reads 0).
 
-Parameters live in one flat fp32 buffer in Keras layouts (Dense kernel [in, out]) under the Keras names of the inner layers
-(`dense_block1_fc.W`, `dense_block2_bn.gamma`, `attention1_input.b`, `outputs.W`), so a checkpoint maps 1:1.  Initialisation as
-Keras: glorot_uniform kernels, zero biases, BatchNormalization 1 / 0 / 0 / 1.
+Parameters carry the Keras names of the inner layers (`dense_block1_fc.W`, `dense_block2_bn.gamma`, `attention1_input.b`,
+`outputs.W`).
 """
 import ctypes
-import math
 
-import numpy as np
 import torch
 
 from .. import _native as nv
+from .flat import FlatModel, Workspace, _rows
 from .gru_rnn import BatchNormSpec
-from .rnn import RecurrentModel
-from .tdnn import DenseSpec, _rows
+from .tdnn import DenseSpec
 
 MAX_OUTPUTS = 1024          # lidbox_mla_attention_*: a row of class logits lives in the registers of one wave
 
 
-def _align4(n):
-    return (n + 3) & ~3
-
-
-class _Workspace:
+class _Workspace(Workspace):
     """All per-(B, T) device buffers of one multilevel_attention model."""
 
     def __init__(self, model, B, T):
@@ -84,33 +76,21 @@ class _Workspace:
         self.bn_ws = torch.empty(max(16, lib.lidbox_bn_workspace(max(R, 1), H)), dtype=torch.uint8, device=dev)
         self.pending = []
 
-    def input_view(self):
-        return self.x
 
-    def input_target(self):
-        """(pointer, floats between utterances, T, C) of the model input buffer (what Trainer / _load_input fill)"""
-        return ctypes.c_void_p(self.x.data_ptr()), self.x.stride(0), self.x.shape[1], self.x.shape[2]
+class MultilevelAttentionModel(FlatModel):
+    """L x (Dense -> BatchNormalization -> ReLU -> Dropout, with an attention pooling of its output) -> Concatenate -> Dense
+    (see the module docstring)."""
 
-
-class MultilevelAttentionModel(RecurrentModel):
-    """L x (Dense -> BatchNormalization -> ReLU -> Dropout, with an attention pooling of its output) -> Concatenate -> Dense.
-    Shares the public calls of `RecurrentModel` (parameter access, input loading, __call__); see the module docstring."""
+    workspace_class = _Workspace
 
     def __init__(self, input_shape, num_outputs, L=2, H=512, dropout_rate=0.4, name="DNN_multilevel_attention",
                  output_activation="log_softmax", seed=None, device=None, compute_dtype="float32"):
-        if compute_dtype not in ("float32", "fp32", "f32", torch.float32):
-            raise ValueError("multilevel_attention computes in float32 only, got compute_dtype=%r" % (compute_dtype,))
-        if output_activation not in (None, "log_softmax", "softmax"):
-            raise ValueError("output_activation must be None, 'log_softmax' or 'softmax', got %r" % (output_activation,))
+        super().__init__(input_shape, name, output_activation, seed, device, compute_dtype)
         if int(L) < 1 or int(H) < 1 or not 1 <= int(num_outputs) <= MAX_OUTPUTS:
             raise ValueError("multilevel_attention needs L >= 1, H >= 1 and 1 <= num_outputs <= %d, got L=%r, H=%r, num_outputs=%r"
                              % (MAX_OUTPUTS, L, H, num_outputs))
         if not 0.0 <= float(dropout_rate) < 1.0:
             raise ValueError("dropout_rate must be in [0, 1)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.name = name
-        self.input_shape = tuple(input_shape)
-        self.input_dim = self.model_input_dim = int(input_shape[-1])
         self.levels, self.units, self.output_dim = int(L), int(H), int(num_outputs)
         self.dropout_rate = float(dropout_rate)
         self.blocks = ["dense_block%d" % (l + 1) for l in range(self.levels)]
@@ -118,95 +98,19 @@ class MultilevelAttentionModel(RecurrentModel):
         self.attentions = ["attention%d_input" % (l + 1) for l in range(self.levels)]
         self.out = DenseSpec("outputs", self.output_dim, relu=False)
         self.denses = [self.out]
-        self.head = "last"
-        self.lstms = []
-        self.output_activation = output_activation
-        self.channel_dropout_rate = 0.0
-        self.dropout_seed = int(np.random.default_rng(seed).integers(1, 2 ** 62))
-        self._dropout_calls = 0
-        self.compute_dtype = "float32"
-        # what lidbox_amd.train.Trainer reads from every model
-        self.convs, self.frontend, self.bf16_storage, self.attention = [], None, False, None
-        self.wgrad_stream = None
-        self.head_wgrad_stream = None
-        self.layout, self.state_layout = {}, {}
-        off, soff = 0, 0
-
-        def entry(pname, shape):
-            nonlocal off
-            self.layout[pname] = (off, shape)
-            off = _align4(off + int(np.prod(shape)))
-
         Hn, K = self.units, self.output_dim
         cin = self.input_dim
         for l in range(self.levels):
-            fc, bn, at = self.blocks[l] + "_fc", self.bns[l].name, self.attentions[l]
-            entry(fc + ".W", (cin, Hn))
-            entry(fc + ".b", (Hn,))
-            entry(bn + ".gamma", (Hn,))
-            entry(bn + ".beta", (Hn,))
-            for suffix in (".moving_mean", ".moving_variance"):
-                self.state_layout[bn + suffix] = (soff, (Hn,))
-                soff = _align4(soff + Hn)
-            entry(at + ".W", (Hn, K))
-            entry(at + ".b", (K,))
+            fc, at = self.blocks[l] + "_fc", self.attentions[l]
+            self.add_param(fc + ".W", (cin, Hn))
+            self.add_param(fc + ".b", (Hn,))
+            self.add_bn(self.bns[l].name, Hn)
+            self.add_param(at + ".W", (Hn, K))
+            self.add_param(at + ".b", (K,))
             cin = Hn
-        entry("outputs.W", (self.levels * K, K))
-        entry("outputs.b", (K,))
-        self.num_flat = off
-        self.flat = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.flat_grad = torch.zeros_like(self.flat)
-        self.state = torch.zeros(max(soff, 4), dtype=torch.float32, device=self.device)
-        self._init_weights(seed)
-        self._ws = {}
-
-    # ------------------------------------------------------------------ parameters
-    def _init_weights(self, seed):
-        """Keras defaults: glorot_uniform kernels, zero biases, gamma 1, beta 0, moving mean 0, moving variance 1"""
-        rng = np.random.default_rng(seed)
-        host = np.zeros(self.num_flat, np.float32)
-        for name, (off, shape) in self.layout.items():
-            n = int(np.prod(shape))
-            if name.endswith(".W"):
-                limit = math.sqrt(6.0 / (shape[0] + shape[1]))
-                host[off:off + n] = rng.uniform(-limit, limit, size=n).astype(np.float32)
-            elif name.endswith(".gamma"):
-                host[off:off + n] = 1.0
-        self.flat.copy_(torch.from_numpy(host))
-        self.state.zero_()
-        for name, (off, shape) in self.state_layout.items():
-            if name.endswith(".moving_variance"):
-                self.state[off:off + shape[0]] = 1.0
-
-    def param(self, name, grad=False):
-        if name in self.state_layout:
-            off, shape = self.state_layout[name]
-            return self.state[off:off + int(np.prod(shape))].view(shape)
-        return super().param(name, grad)
-
-    def count_params(self):
-        """Keras `Model.count_params()`: the Dense layers and 4H per BatchNormalization (gamma, beta and the two moving
-        statistics)"""
-        return sum(int(np.prod(s)) for _, s in list(self.layout.values()) + list(self.state_layout.values()))
-
-    def get_weights(self):
-        """dict name -> numpy array in Keras layouts (trainable parameters and the BatchNormalization moving statistics)"""
-        return {n: self.param(n).detach().cpu().numpy().copy() for n in list(self.layout) + list(self.state_layout)}
-
-    def _sp(self, name):
-        off, _ = self.state_layout[name]
-        return ctypes.c_void_p(self.state.data_ptr() + 4 * off)
-
-    # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T):
-        key = (int(B), int(T))
-        ws = self._ws.get(key)
-        if ws is None:
-            if len(self._ws) >= 4:
-                self._ws.pop(next(iter(self._ws)))
-            ws = _Workspace(self, *key)
-            self._ws[key] = ws
-        return ws
+        self.add_param("outputs.W", (self.levels * K, K))
+        self.add_param("outputs.b", (K,))
+        self._finish(seed)
 
     def _in_rows(self, ws, l):
         """(rows descriptor, width) of level l's input: the model input, or the previous level's output"""
@@ -247,17 +151,7 @@ class MultilevelAttentionModel(RecurrentModel):
             X, cin = self._in_rows(ws, l)
             nv.check(lib.lidbox_gemm_nn(X, self._p(fc + ".W"), H, _rows(ws.a[l].data_ptr(), 0, H, 1, R), cin, H, nv.EPI_BIAS,
                                         self._p(fc + ".b"), gws, gws_n, st))
-            cp = [ctypes.c_void_p(ws.consts[l].data_ptr() + 4 * j * H) for j in range(4)]
-            if training:
-                mm = self._sp(bn.name + ".moving_mean") if update_moving else None
-                mv = self._sp(bn.name + ".moving_variance") if update_moving else None
-                nv.check(lib.lidbox_bn_train_stats_ex(nv.ptr(ws.a[l]), R, H, self._p(bn.name + ".gamma"), self._p(bn.name + ".beta"),
-                                                      bn.epsilon, bn.momentum, 0, mm, mv, cp[0], cp[1], cp[2], cp[3],
-                                                      nv.ptr(ws.bn_ws), ws.bn_ws.numel(), st))
-            else:
-                nv.check(lib.lidbox_bn_infer_consts(self._p(bn.name + ".gamma"), self._p(bn.name + ".beta"),
-                                                    self._sp(bn.name + ".moving_mean"), self._sp(bn.name + ".moving_variance"),
-                                                    bn.epsilon, H, cp[2], cp[3], st))
+            cp = self._bn_fwd(bn, ws.a[l], R, H, ws.consts[l], None, ws, training, update_moving)
             nv.check(lib.lidbox_bn_relu_dropout_fwd(nv.ptr(ws.a[l]), R, H, cp[2], cp[3], rate, self.level_dropout_seed(l),
                                                     self._dropout_step_ptr(), nv.ptr(ws.y[l]), st))
             nv.check(lib.lidbox_gemm_nn(_rows(ws.y[l].data_ptr(), 0, H, 1, R), self._p(at + ".W"), K,
@@ -269,11 +163,7 @@ class MultilevelAttentionModel(RecurrentModel):
         nv.check(lib.lidbox_gemm_nn(_rows(ws.att.data_ptr(), 0, L * K, 1, B), self._p("outputs.W"), K,
                                     _rows(ws.h[-1].data_ptr(), 0, K, 1, B), L * K, K, nv.EPI_BIAS, self._p("outputs.b"),
                                     gws, gws_n, st))
-        if self.output_activation is None:
-            return ws.h[-1]
-        fn = lib.lidbox_softmax_fwd if self.output_activation == "softmax" else lib.lidbox_log_softmax_fwd
-        nv.check(fn(nv.ptr(ws.h[-1]), B, K, nv.ptr(ws.logp), st))
-        return ws.logp
+        return self._output_activation(ws, ws.h[-1], K)
 
     # ------------------------------------------------------------------ backward
     def backward_head_ws(self, ws):
@@ -315,9 +205,7 @@ class MultilevelAttentionModel(RecurrentModel):
                                                     ctypes.c_void_p(c.data_ptr() + 4 * 3 * H), self.dropout_rate,
                                                     self.level_dropout_seed(l), self._dropout_step_ptr(), nv.ptr(ws.dy),
                                                     nv.ptr(ws.dy), st))
-            nv.check(lib.lidbox_bn_bwd(nv.ptr(ws.a[l]), dy, R, H, ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(c.data_ptr() + 4 * H),
-                                       self._p(bn.name + ".gamma"), 0, self._p(bn.name + ".gamma", True),
-                                       self._p(bn.name + ".beta", True), nv.ptr(ws.da), nv.ptr(ws.bn_ws), ws.bn_ws.numel(), st))
+            self._bn_bwd(bn, ws.a[l], R, H, c, ws.dy, 0, ws.da, ws)
             # dense_block{l}_fc
             X, cin = self._in_rows(ws, l)
             nv.check(lib.lidbox_gemm_tn(X, da, self._p(fc + ".W", True), H, cin, H, 0, self._p(fc + ".b", True), tws, tws_n, st))

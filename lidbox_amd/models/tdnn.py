@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _native as nv
+from .flat import FlatParams, Workspace, _align4, _rows
 
 
 class ConvSpec:
@@ -111,14 +112,6 @@ def conv_out_len(T, s):
     return (T - 1) // s + 1 if T > 0 else 0
 
 
-def _align4(n):
-    return (n + 3) & ~3
-
-
-def _rows(t_ptr, batch_stride, row_stride, batch, rpb):
-    return nv.Rows(t_ptr, int(batch_stride), int(row_stride), int(batch), int(rpb))
-
-
 class _GemmFamily:
     """The C-ABI entry points of one GEMM family: fp32 MFMA (gemm.hip) or bf16 MFMA with fp32 storage and
     accumulation (gemm_bf16.hip, BASELINE config 5).  Same signatures, separate workspace sizing.  Entry points
@@ -141,7 +134,7 @@ class _GemmFamily:
         return getattr(nv.lib, self._prefix + op)
 
 
-class _Workspace:
+class _Workspace(Workspace):
     """All per-(B, T) device buffers of one model."""
 
     def __init__(self, model, B, T):
@@ -289,14 +282,11 @@ class _Workspace:
             return self.fe_in
         return self.act[0][:, self.pads[0]:, :]
 
-    def input_target(self):
-        """(pointer, floats between utterances, T, C) of the model input buffer (what Trainer / _load_input fill)"""
-        v = self.input_view()
-        return ctypes.c_void_p(v.data_ptr()), v.stride(0), v.shape[1], v.shape[2]
 
+class SequentialTDNN(FlatParams):
+    """convs -> pool -> denses -> log_softmax, parameters in one flat buffer (accessors and workspace cache: models/flat.py)."""
 
-class SequentialTDNN:
-    """convs -> pool -> denses -> log_softmax, parameters in one flat buffer."""
+    workspace_class = _Workspace
 
     def __init__(self, input_shape, convs, pool, denses, name="tdnn", output_activation="log_softmax",
                  channel_dropout_rate=0.0, seed=None, device=None, compute_dtype="float32", attention=None, frontend=None):
@@ -455,29 +445,6 @@ class SequentialTDNN:
         for name, (off, shape) in self.state_layout.items():
             self.state[off:off + shape[0]] = 1.0 if name.endswith("moving_variance") else 0.0
 
-    def param(self, name, grad=False):
-        if name in self.state_layout:
-            off, shape = self.state_layout[name]
-            return self.state[off:off + int(np.prod(shape))].view(shape)
-        off, shape = self.layout[name]
-        buf = self.flat_grad if grad else self.flat
-        return buf[off:off + int(np.prod(shape))].view(shape)
-
-    def named_parameters(self):
-        return [(n, self.param(n)) for n in self.layout]
-
-    def count_params(self):
-        """Keras `Model.count_params()`: trainable + non-trainable (BatchNormalization moving statistics)"""
-        return sum(int(np.prod(s)) for _, s in list(self.layout.values()) + list(self.state_layout.values()))
-
-    def get_weights(self):
-        """dict name -> numpy array in Keras layouts (trainable parameters and the BatchNormalization moving statistics)."""
-        return {n: self.param(n).detach().cpu().numpy().copy() for n in list(self.layout) + list(self.state_layout)}
-
-    def set_weights(self, weights):
-        for n, w in weights.items():
-            self.param(n).copy_(torch.as_tensor(np.asarray(w, np.float32)).to(self.device).reshape(self.param(n).shape))
-
     def _cin(self, i):
         return self.input_dim if i == 0 else self.convs[i - 1].filters
 
@@ -569,30 +536,10 @@ class SequentialTDNN:
         return nv.Rows(t16.data_ptr() + 2 * (r * C16 + col), view_rows.batch_stride // C * C16, view_rows.row_stride // C * C16,
                        view_rows.batch, view_rows.rows_per_batch)
 
-    def _sp(self, name):
-        off, _ = self.state_layout[name]
-        return ctypes.c_void_p(self.state.data_ptr() + 4 * off)
-
     def fe_gemm(self, i):
         """GEMM family of front-end layer i: the first one contracts over k = 5 single-channel taps (row stride 1 float),
         which the bf16 family's 16-byte operand rule excludes -- it always runs in the fp32 family"""
         return self.gemm if i > 0 else _GemmFamily("float32")
-
-    def _p(self, name, grad=False):
-        off, _ = self.layout[name]
-        base = (self.flat_grad if grad else self.flat).data_ptr()
-        return ctypes.c_void_p(base + 4 * off)
-
-    # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T):
-        key = (int(B), int(T))
-        ws = self._ws.get(key)
-        if ws is None:
-            if len(self._ws) >= 4:                     # keep the cache small
-                self._ws.pop(next(iter(self._ws)))
-            ws = _Workspace(self, *key)
-            self._ws[key] = ws
-        return ws
 
     # ------------------------------------------------------------------ forward
     def _conv_rows_in(self, ws, i):

@@ -50,7 +50,7 @@ def recurrence_ms(B, H=62):
     ws.dseq[0].copy_(torch.from_numpy(rng.standard_normal(tuple(ws.dseq[0].shape)).astype(np.float32)))
     zg0 = ws.zg[0].clone()
     l = m.lstms[0]
-    U0, U1 = m._U(l)
+    U0, U1 = (m._p(p + ".U") for p in l.prefixes)
     st = nv.current_stream()
 
     def fwd():
