@@ -49,16 +49,16 @@ def _run(x, W, b, dyv, taps, Co, dgrad=True):
     B, T, F, Ci = x.shape
     xd, Wd, bd = (torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda() for a in (x, W, b))
     y0 = _torch_conv(torch.from_numpy(x), torch.from_numpy(W), taps)
-    y = torch.zeros(y0.shape, dtype=torch.float32, device="cuda")
+    y = torch.full(y0.shape, float("nan"), dtype=torch.float32, device="cuda")
     nv.check(nv.lib.lidbox_conv2d_strided_fwd(nv.ptr(xd), B, T, F, Ci, nv.ptr(Wd), taps, Co, nv.ptr(bd), nv.ptr(y), st))
     dyd = torch.from_numpy(dyv.astype(np.float32)).cuda()
     dx = None
     if dgrad:
-        dx = torch.zeros_like(xd)
+        dx = torch.full_like(xd, float("nan"))
         wsb = nv.lib.lidbox_conv2d_strided_dgrad_workspace(taps, Ci, Co)
         ws = torch.empty(max(16, wsb), dtype=torch.uint8, device="cuda")
         nv.check(nv.lib.lidbox_conv2d_strided_dgrad(nv.ptr(dyd), B, T, F, Ci, Co, nv.ptr(Wd), taps, nv.ptr(dx), nv.ptr(ws), ws.numel(), st))
-    dW, db = torch.zeros_like(Wd), torch.zeros_like(bd)
+    dW, db = torch.full_like(Wd, float("nan")), torch.full_like(bd, float("nan"))
     wsb = nv.lib.lidbox_conv2d_strided_wgrad_workspace(B, T, F, Ci, Co, taps)
     ws = torch.empty(max(16, wsb), dtype=torch.uint8, device="cuda")
     nv.check(nv.lib.lidbox_conv2d_strided_wgrad(nv.ptr(xd), nv.ptr(dyd), B, T, F, Ci, Co, taps, nv.ptr(dW), nv.ptr(db), nv.ptr(ws),
