@@ -16,38 +16,24 @@
 //     hseq  [B][T+2][dirs*H]   h_t of direction d at row t+1; rows 0 and T+1 stay zero (as in rnn.hip)
 //     carry [dirs][B][H]       backward's direct term z_{t+1} dh_{t+1} (workspace)
 //
-// One form, any H: one launch per time step covers both directions.  Grid = ceil(B / 64) row tiles x ceil(H / 16) unit
-// slices x dirs; a workgroup is 4 waves, wave w owns rows 16w..16w+15 of its tile.  All three gates of unit j read only
-// columns j, H+j and 2H+j of U, so a workgroup computes h_{t-1}[rows, :] U[:, {z, r, h} columns of its 16 units] with
-// v_mfma_f32_16x16x4_f32 (exact fp32) into three accumulators whose (row, unit) positions coincide in every lane, and
-// applies the cell in the same kernel.  Forward stages U's 48 columns of the slice into LDS in 256-row chunks; backward
-// computes dh_rec = dZrec_{t+1} U^T for its units (K = 3H), staging U's 16 rows of the slice in 768-column chunks.  The
-// A operand (h_{t-1} or dZrec_{t+1} rows) streams from global memory: lane (c, g) = (l & 15, l >> 4) loads row c, k =
-// k0 + 8g .. k0 + 8g + 7, and MFMA e of the k0 block consumes element e -- a fixed permutation of the k order.
+// One form, any H: the step pipeline of rnn_step.h with its GruStep parameters (three gates: 48 columns of U per slice in
+// 256-row chunks forward, 768-column chunks backward, one A block in flight, issued after the staging).  Backward's K = 3H
+// runs over three sources -- (dz, dr) from zg and dhh * r from qh -- so U is staged one gate block at a time.
+//
+// Load paths: float4 when H % 4 == 0 and every buffer is 16-byte aligned (then every row and chunk start is aligned too),
+// scalar otherwise; both feed the MFMAs in the same k order and give the same bits.
 //
 // No inter-workgroup communication, no atomics, no spin-waits: steps are ordered by the stream alone.  Every output element
 // is one MFMA k-chain over its own row, in an order that depends on neither B nor the row's place in the batch, so a
 // row's results are bit-identical whatever the batch.
 #include <math.h>
 
-#include "common.h"
+#include "rnn_step.h"
 
 // No a*b+c is contracted behind the source's back (as in rnn.hip): the cell is evaluated exactly as written.
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int GRU_ROWS = 64;     // batch rows per workgroup: 4 waves x 16
-constexpr int GRU_UNITS = 16;    // hidden units per workgroup: 48 columns of U forward, 16 rows of U backward
-constexpr int GRU_KCF = 256;     // forward: rows of U per LDS chunk (256 x 50 floats = 50 KiB)
-constexpr int GRU_KCB = 768;     // backward: columns of U per LDS chunk (768 x 18 floats = 54 KiB)
-// LDS row strides: 8 * ld = 16 (mod 64 banks), so the four k groups of a wave (rows k, k+8, k+16, k+24) hit disjoint banks
-constexpr int GRU_LDF = 50;
-constexpr int GRU_LDB = 18;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct GruArgs {
     const float* U[2];
@@ -63,127 +49,17 @@ struct GruArgs {
     int B, T, H, dirs;
 };
 
-// this lane's A values k .. k+7 of a chunk (zeros past klen or for a row past B)
-template <bool VEC>
-__device__ __forceinline__ void load_a(float (&av)[8], const float* __restrict__ arow, bool aok, int k, int klen) {
-    if (VEC) {
-        float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-        if (aok && k < klen) v0 = *reinterpret_cast<const float4*>(arow + k);
-        if (aok && k + 4 < klen) v1 = *reinterpret_cast<const float4*>(arow + k + 4);
-        av[0] = v0.x; av[1] = v0.y; av[2] = v0.z; av[3] = v0.w;
-        av[4] = v1.x; av[5] = v1.y; av[6] = v1.z; av[7] = v1.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) av[e] = aok && k + e < klen ? arow[k + e] : 0.0f;
-    }
-}
-
-// acc[g] += A[16 rows of this wave][kc .. kc+klen) . Bs[k][16 g + c].  arow: this lane's A row at the chunk start (row
-// l & 15 of the wave; aok false: a row past B, which contributes zeros).  Bs holds kpad = klen rounded up to 32 rows, zero
-// past klen.  VEC: klen % 4 == 0 and arow 16-byte aligned.  The next block's A values are loaded before this block's MFMAs.
-template <int NG, bool VEC>
-__device__ __forceinline__ void mma_chunk(f32x4 (&acc)[NG], const float* __restrict__ arow, bool aok, int klen, int kpad,
-                                          const float* Bs, int ldb, int lane) {
-    const int c = lane & 15, kg = lane >> 4;
-    float av[8], an[8];
-    load_a<VEC>(an, arow, aok, 8 * kg, klen);
-    for (int k0 = 0; k0 < kpad; k0 += 32) {
-        const int k = k0 + 8 * kg;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) av[e] = an[e];
-        if (k0 + 32 < kpad) load_a<VEC>(an, arow, aok, k + 32, klen);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float* br = Bs + (k + e) * ldb + c;
-#pragma unroll
-            for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], br[g * 16], acc[g], 0, 0, 0);
-        }
-    }
-}
-
-// LDS staging of n items by the workgroup's 256 threads: GRU_STAGE_BATCH loads in flight per thread before their stores
-// (a load-store loop would wait out one memory latency per item)
-constexpr int GRU_STAGE_BATCH = 12;
-
-template <typename V, typename Load, typename Store>
-__device__ __forceinline__ void stage(int n, Load load, Store store) {
-    for (int base = threadIdx.x; base < n; base += 256 * GRU_STAGE_BATCH) {
-        V v[GRU_STAGE_BATCH];
-#pragma unroll
-        for (int j = 0; j < GRU_STAGE_BATCH; ++j) {
-            const int i = base + 256 * j;
-            if (i < n) v[j] = load(i);
-        }
-#pragma unroll
-        for (int j = 0; j < GRU_STAGE_BATCH; ++j) {
-            const int i = base + 256 * j;
-            if (i < n) store(i, v[j]);
-        }
-    }
-}
-
-// forward chunk: Bs[kk][16 g + c] = U[kc + kk][g H + u0 + c] (zero past klen / H); float4 loads along the units when VEC
-template <bool VEC>
-__device__ __forceinline__ void stage_fwd(float* Bs, const float* __restrict__ U, int H, int u0, int kc, int klen, int kpad) {
-    const size_t H3 = 3 * (size_t)H;
-    if (VEC) {
-        stage<float4>(kpad * 12, [&](int e) {
-            const int kk = e / 12, q = e - kk * 12, u = u0 + 4 * (q & 3);
-            return kk < klen && u < H ? *reinterpret_cast<const float4*>(U + (kc + kk) * H3 + (q >> 2) * H + u)
-                                      : make_float4(0.f, 0.f, 0.f, 0.f);
-        }, [&](int e, float4 v) {
-            const int kk = e / 12, q = e - kk * 12;
-            float* d = Bs + kk * GRU_LDF + 4 * q;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        });
-    } else {
-        stage<float>(kpad * 48, [&](int e) {
-            const int kk = e / 48, j = e - kk * 48, u = u0 + (j & 15);
-            return kk < klen && u < H ? U[(kc + kk) * H3 + (j >> 4) * H + u] : 0.0f;
-        }, [&](int e, float v) {
-            const int kk = e / 48, j = e - kk * 48;
-            Bs[kk * GRU_LDF + j] = v;
-        });
-    }
-}
-
-// backward chunk of gate block q: Bs[kk][c] = U[u0 + c][q H + kc + kk] (zero past klen / H); float4 loads along k when VEC
-template <bool VEC>
-__device__ __forceinline__ void stage_bwd(float* Bs, const float* __restrict__ U, int H, int u0, int q, int kc, int klen,
-                                          int kpad) {
-    const size_t H3 = 3 * (size_t)H;
-    if (VEC) {
-        const int k4n = kpad / 4;
-        stage<float4>(16 * k4n, [&](int e) {
-            const int c = e / k4n, k4 = 4 * (e - c * k4n), u = u0 + c;
-            return k4 < klen && u < H ? *reinterpret_cast<const float4*>(U + u * H3 + q * H + kc + k4)
-                                      : make_float4(0.f, 0.f, 0.f, 0.f);
-        }, [&](int e, float4 v) {
-            const int c = e / k4n, k4 = 4 * (e - c * k4n);
-            float* d = Bs + k4 * GRU_LDB + c;
-            d[0] = v.x; d[GRU_LDB] = v.y; d[2 * GRU_LDB] = v.z; d[3 * GRU_LDB] = v.w;
-        });
-    } else {
-        stage<float>(16 * kpad, [&](int e) {
-            const int c = e / kpad, kk = e - c * kpad, u = u0 + c;
-            return kk < klen && u < H ? U[u * H3 + q * H + kc + kk] : 0.0f;
-        }, [&](int e, float v) {
-            const int c = e / kpad, kk = e - c * kpad;
-            Bs[kk * GRU_LDB + c] = v;
-        });
-    }
-}
-
 // one forward step s of both directions (direction d: t = s forward, T-1-s reverse)
 template <bool VEC>
 __global__ __launch_bounds__(256) void gru_fwd_step_kernel(const GruArgs a, int s) {
-    __shared__ __attribute__((aligned(16))) float Bs[GRU_KCF * GRU_LDF];
+    __shared__ __attribute__((aligned(16))) float Bs[GruStep::KCF * STEP_LDF<GruStep>];
+    constexpr int VW = VEC ? 4 : 1;
     const int H = a.H, T = a.T, B = a.B, d = blockIdx.z, H3 = 3 * H, ldo = a.dirs * H;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int u0 = blockIdx.y * GRU_UNITS;
+    const int u0 = blockIdx.y * STEP_UNITS;
     const int t = d == 0 ? s : T - 1 - s;
     const int prow = d == 0 ? t : t + 2;                      // hseq row of h_{t-1} (forward) / h_{t+1} (reverse)
-    const int rb = blockIdx.x * GRU_ROWS + w * 16;
+    const int rb = blockIdx.x * STEP_ROWS + w * 16;
     f32x4 acc[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -192,12 +68,12 @@ __global__ __launch_bounds__(256) void gru_fwd_step_kernel(const GruArgs a, int 
         const bool aok = ra < B;
         const float* arow = a.hseq + ((size_t)(aok ? ra : 0) * (T + 2) + prow) * ldo + d * H;
         const float* U = a.U[d];
-        for (int kc = 0; kc < H; kc += GRU_KCF) {
-            const int klen = min(GRU_KCF, H - kc), kpad = (klen + 31) & ~31;
+        for (int kc = 0; kc < H; kc += GruStep::KCF) {
+            const int klen = min(GruStep::KCF, H - kc), kpad = (klen + 31) & ~31;
             __syncthreads();                                  // the previous chunk's LDS reads are done
-            stage_fwd<VEC>(Bs, U, H, u0, kc, klen, kpad);
+            stage_fwd<GruStep, VW>(Bs, U, H, u0, kc, klen, kpad);
             __syncthreads();
-            mma_chunk<3, VEC>(acc, arow + kc, aok, klen, kpad, Bs, GRU_LDF, lane);
+            mma_chunk<3, VW, GruStep::PF>(acc, arow + kc, aok, klen, kpad, Bs, STEP_LDF<GruStep>, lane);
         }
     }
     // epilogue: lane (c, g) holds unit u0 + c of rows rb + 4g + i (the 16x16 C/D map: col = lane & 15, row = 4 (lane >> 4) + i)
@@ -228,13 +104,14 @@ __global__ __launch_bounds__(256) void gru_fwd_step_kernel(const GruArgs a, int 
 // one backward step s (walked from T-1 down): dh_t = incoming + dZrec_{t+1} U^T + z_{t+1} dh_{t+1}, then the cell backward
 template <bool VEC>
 __global__ __launch_bounds__(256) void gru_bwd_step_kernel(const GruArgs a, int s) {
-    __shared__ __attribute__((aligned(16))) float Bs[GRU_KCB * GRU_LDB];
+    __shared__ __attribute__((aligned(16))) float Bs[GruStep::KCB * STEP_LDB];
+    constexpr int VW = VEC ? 4 : 1;
     const int H = a.H, T = a.T, B = a.B, d = blockIdx.z, H3 = 3 * H, ldo = a.dirs * H;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int u0 = blockIdx.y * GRU_UNITS;
+    const int u0 = blockIdx.y * STEP_UNITS;
     const int t = d == 0 ? s : T - 1 - s;
     const int prow = d == 0 ? t : t + 2;
-    const int rb = blockIdx.x * GRU_ROWS + w * 16;
+    const int rb = blockIdx.x * STEP_ROWS + w * 16;
     f32x4 acc[1];
     acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (s < T - 1) {                                          // the direction's last step has no later step
@@ -245,12 +122,12 @@ __global__ __launch_bounds__(256) void gru_bwd_step_kernel(const GruArgs a, int 
         const float* U = a.U[d];
         for (int q = 0; q < 3; ++q) {                         // dZrec = (dz, dr) from zg, dhh * r from qh
             const float* arow = q < 2 ? a.zg + nrow * H3 + q * H : a.qh + nrow * H;
-            for (int kc = 0; kc < H; kc += GRU_KCB) {
-                const int klen = min(GRU_KCB, H - kc), kpad = (klen + 31) & ~31;
+            for (int kc = 0; kc < H; kc += GruStep::KCB) {
+                const int klen = min(GruStep::KCB, H - kc), kpad = (klen + 31) & ~31;
                 __syncthreads();
-                stage_bwd<VEC>(Bs, U, H, u0, q, kc, klen, kpad);
+                stage_bwd<GruStep, VEC>(Bs, U + q * H, H, u0, kc, klen, kpad);   // gate block q: columns q H .. of U's rows
                 __syncthreads();
-                mma_chunk<1, VEC>(acc, arow + kc, aok, klen, kpad, Bs, GRU_LDB, lane);
+                mma_chunk<1, VW, GruStep::PF>(acc, arow + kc, aok, klen, kpad, Bs, STEP_LDB, lane);
             }
         }
     }
@@ -281,25 +158,9 @@ __global__ __launch_bounds__(256) void gru_bwd_step_kernel(const GruArgs a, int 
     }
 }
 
-int check_common(const char* fn, const float* U0, const float* U1, int dirs, int B, int T, int H) {
-    if (!(dirs == 1 || dirs == 2) || !U0 || (dirs == 2 && !U1) || B < 0 || T < 1 || H < 1) {
-        lidbox_set_error("%s: invalid argument: dirs in {1, 2}, U0 (and U1 when dirs == 2) != NULL, B >= 0, T >= 1, H >= 1", fn);
-        return LIDBOX_E_INVALID;
-    }
-    if (H > 65535 || (long)B * T * 3 * H > (1L << 40)) {
-        lidbox_set_error("%s: invalid argument: H <= 65535, B * T * 3H <= 2^40", fn);
-        return LIDBOX_E_INVALID;
-    }
-    return LIDBOX_OK;
-}
-
-// float4 operand loads: H % 4 == 0 and 16-byte aligned buffers (then every row and chunk start is aligned too)
+// float4 operand loads
 inline bool vec_ok(int H, const void* U0, const void* U1, const void* zg, const void* hseq, const void* qh) {
-    return H % 4 == 0 && (((uintptr_t)U0 | (uintptr_t)U1 | (uintptr_t)zg | (uintptr_t)hseq | (uintptr_t)qh) & 15) == 0;
-}
-
-inline dim3 step_grid(int B, int H, int dirs) {
-    return dim3((unsigned)lbx_cdiv(B, GRU_ROWS), (unsigned)lbx_cdiv(H, GRU_UNITS), (unsigned)dirs);
+    return H % 4 == 0 && aligned_to(16, U0, U1, zg, hseq, qh);
 }
 
 }  // namespace
@@ -311,7 +172,7 @@ extern "C" size_t lidbox_gru_workspace(int B, int T, int H, int dirs) {
 
 extern "C" int lidbox_gru_fwd(const float* U0, const float* U1, const float* b_rec0, const float* b_rec1, int dirs, int B,
                               int T, int H, float* zg, float* hseq, float* qh, float* hlast, lidbox_stream_t stream) {
-    if (int e = check_common(__func__, U0, U1, dirs, B, T, H)) return e;
+    if (int e = check_step_args(__func__, 3, U0, U1, dirs, B, T, H)) return e;
     LBX_ARG(b_rec0 && (dirs == 1 || b_rec1) && zg && hseq && qh, "b_rec0 (and b_rec1 when dirs == 2), zg, hseq, qh != NULL");
     if (B == 0) return LIDBOX_OK;
     GruArgs a{{U0, dirs == 2 ? U1 : U0}, {b_rec0, dirs == 2 ? b_rec1 : b_rec0}, zg, hseq, qh, hlast, nullptr, 0, nullptr,
@@ -332,7 +193,7 @@ extern "C" int lidbox_gru_fwd(const float* U0, const float* U1, const float* b_r
 extern "C" int lidbox_gru_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* hseq,
                               float* qh, const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace,
                               size_t workspace_bytes, lidbox_stream_t stream) {
-    if (int e = check_common(__func__, U0, U1, dirs, B, T, H)) return e;
+    if (int e = check_step_args(__func__, 3, U0, U1, dirs, B, T, H)) return e;
     LBX_ARG(zg && hseq && qh && (dh_seq || dh_last), "zg, hseq, qh != NULL; dh_seq or dh_last != NULL");
     LBX_ARG(!dh_seq || dh_batch_stride >= (long)T * dirs * H, "dh_batch_stride >= T * dirs * H");
     if (B == 0) return LIDBOX_OK;

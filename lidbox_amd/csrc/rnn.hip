@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "rnn_cell.h"
 
 // No a*b+c is contracted behind the source's back: whether it becomes an FMA could then depend on how the compiler
 // vectorises the rows of a thread (RT), and a row's bits on B.  The FMAs that are meant are written as fmaf.
@@ -46,8 +47,6 @@ namespace {
 
 constexpr int LSTM_RESIDENT_MAX_H = 80;   // LDS: U image 16 Hp^2 + 4 Hp bytes (102 720 B at Hp = 80) + backward's dZ tiles
 constexpr int LSTM_LDS_BUDGET = 160 * 1024;
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 inline int pad16(int H) { return (H + 15) & ~15; }
 
@@ -172,18 +171,6 @@ __global__ __launch_bounds__(4 * LSTM_RESIDENT_MAX_H) void lstm_resident_fwd_ker
         __syncthreads();
         p ^= 1;
     }
-}
-
-// cell backward of one (row, unit): gates a = {i, f, g, o}, returns dZ in a, updates dc
-__device__ __forceinline__ void cell_bwd(float a[4], float ct, float cprev, float dh, float& dc) {
-    const float ig = a[0], fg = a[1], gg = a[2], og = a[3];
-    const float tc = tanhf(ct);
-    const float dct = dc + dh * og * (1.0f - tc * tc);
-    a[0] = dct * gg * ig * (1.0f - ig);
-    a[1] = dct * cprev * fg * (1.0f - fg);
-    a[2] = dct * ig * (1.0f - gg * gg);
-    a[3] = dh * tc * og * (1.0f - og);
-    dc = dct * fg;
 }
 
 template <int RT>

@@ -25,3 +25,15 @@ def synthetic_batch(batch_size, num_labels=4, sample_rate=16000, duration_s=2.0,
     tone = np.sin(2.0 * np.pi * freqs[:, None] * t[None, :])
     noise = rng.normal(0.0, 0.1, size=(batch_size, n)) ** 2
     return peak_normalize(tone + noise, -3.0).astype(np.float32), labels
+
+
+def device_copy(a, misalign=False):
+    """float32 array a as a tensor on the GPU; misalign: one float into a larger allocation, so that its pointer is 4 bytes
+    past a multiple of 16 (kernels that choose their load width by pointer alignment then take their scalar path)."""
+    import torch
+    if not misalign:
+        return torch.from_numpy(a).cuda().contiguous()
+    t = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")[1:].view(a.shape)
+    t.copy_(torch.from_numpy(a))
+    assert t.data_ptr() % 16 == 4
+    return t

@@ -8,6 +8,8 @@ reset_after form.  The model oracle is a float64 transcription of reference lidb
 Tolerances: the first measured layer errors (MI355X; every case of LAYER_CASES: H in {1, 10, 62, 100, 512}, T up to 198,
 B up to 256) were at most 3.1e-7 absolute on h and 5.1e-7 relative L2 on dX, dW, dU and both bias rows; the bounds below,
 5e-5 and 1e-4, keep a margin of more than 100x.
+H = 800 and 801 split backward's K per gate into two LDS chunks (float4 and scalar path); the scalar path that only
+misaligned buffers select at H % 4 == 0 is compared bit for bit with the float4 path.  Both hold the same bounds.
 """
 import math
 import os
@@ -90,21 +92,23 @@ def _oracle(params, x, dh_seq=None, dh_last=None):
     return y.detach().numpy(), xt.grad.numpy(), grads
 
 
-def _run_layer(params, x, dh_seq=None, dh_last=None):
+def _run_layer(params, x, dh_seq=None, dh_last=None, misalign=False):
     """the recurrence through the C ABI, with the input projection (and, from dZx / dZrec, the weight gradients) in float64
-    on the host, so that what is compared is the walk through time.  Returns h [B, T, dirs*H], hlast, dZx [dirs, B, T, 3H],
-    the h block of dZrec [dirs, B, T, H] and hseq."""
+    on the host, so that what is compared is the walk through time.  misalign: U of every direction and zg are not 16-byte
+    aligned, which selects the scalar load path whatever H is.  Returns h [B, T, dirs*H], hlast, dZx [dirs, B, T, 3H], the
+    h block of dZrec [dirs, B, T, H] and hseq."""
+    from lidbox_amd.testutil import device_copy
     nv = _nv()
     B, T, C = x.shape
     dirs = len(params)
     H = params[0][1].shape[0]
     dev = torch.device("cuda")
     zg = np.stack([(x.astype(np.float64) @ W.astype(np.float64) + b[0]).astype(np.float32) for W, _, b in params])
-    zg_d = torch.from_numpy(zg).to(dev).contiguous()
+    zg_d = device_copy(zg, misalign)
     hseq = torch.zeros((B, T + 2, dirs * H), dtype=torch.float32, device=dev)
     qh = torch.zeros((dirs, B, T, H), dtype=torch.float32, device=dev)
     hlast = torch.zeros((B, dirs * H), dtype=torch.float32, device=dev)
-    Us = [torch.from_numpy(U).to(dev) for _, U, _ in params]
+    Us = [device_copy(U, misalign) for _, U, _ in params]
     brs = [torch.from_numpy(np.ascontiguousarray(b[1])).to(dev) for _, _, b in params]
     ws = torch.empty(max(16, nv.lib.lidbox_gru_workspace(B, T, H, dirs)), dtype=torch.uint8, device=dev)
     st = nv.current_stream()
@@ -149,7 +153,8 @@ def _check_grads(g, dx, g_ref, dx_ref):
 
 
 LAYER_CASES = [(H, dirs, B, T) for H in (1, 10, 62, 100) for dirs in (1, 2) for (B, T) in ((1, 1), (37, 198), (256, 198))] + \
-              [(512, dirs, B, T) for dirs in (1, 2) for (B, T) in ((1, 1), (37, 60), (256, 16))]
+              [(512, dirs, B, T) for dirs in (1, 2) for (B, T) in ((1, 1), (37, 60), (256, 16))] + \
+              [(800, 2, 3, 3), (801, 1, 3, 3)]     # backward chunks of 768 columns: 768 + 32 (float4), 768 + 33 (scalar)
 
 
 @pytest.mark.parametrize("H,dirs,B,T", LAYER_CASES)
@@ -159,7 +164,11 @@ def test_gru_layer_matches_torch(H, dirs, B, T):
     params = _params(rng, C, H, dirs)
     x = rng.standard_normal((B, T, C)).astype(np.float32)
     dh_seq = rng.standard_normal((B, T, dirs * H)).astype(np.float32)
-    h, hl, dzx, dqh, hseq = _run_layer(params, x, dh_seq=dh_seq)
+    _check_layer(params, x, dh_seq, *_run_layer(params, x, dh_seq=dh_seq))
+
+
+def _check_layer(params, x, dh_seq, h, hl, dzx, dqh, hseq):
+    T, dirs, H = x.shape[1], len(params), params[0][1].shape[0]
     y, dx_ref, g_ref = _oracle(params, x, dh_seq=dh_seq)
     assert np.abs(h - y).max() <= H_TOL, np.abs(h - y).max()
     assert not hseq[:, 0].any() and not hseq[:, T + 1].any()
@@ -168,6 +177,21 @@ def test_gru_layer_matches_torch(H, dirs, B, T):
         assert np.array_equal(hl[:, H:], h[:, 0, H:])
     g, dx = _grads_from_dz(params, x, dzx, dqh, hseq)
     _check_grads(g, dx, g_ref, dx_ref)
+
+
+def test_gru_scalar_path_of_misaligned_buffers_gives_the_same_bits():
+    """H % 4 == 0 takes the float4 kernels unless a buffer is not 16-byte aligned: both load paths feed the MFMAs in the
+    same k order, so every output is bit-identical"""
+    H, dirs, B, T, C = 12, 2, 5, 4, 7
+    rng = np.random.default_rng(H * 1000 + dirs * 100 + B)
+    params = _params(rng, C, H, dirs)
+    x = rng.standard_normal((B, T, C)).astype(np.float32)
+    dh_seq = rng.standard_normal((B, T, dirs * H)).astype(np.float32)
+    aligned = _run_layer(params, x, dh_seq=dh_seq)
+    scalar = _run_layer(params, x, dh_seq=dh_seq, misalign=True)
+    for name, a, b in zip(("h", "hlast", "dZx", "qh", "hseq"), aligned, scalar):
+        assert np.array_equal(a, b), name
+    _check_layer(params, x, dh_seq, *aligned)
 
 
 @pytest.mark.parametrize("H,dirs", [(10, 2), (100, 2), (62, 1)])

@@ -9,6 +9,8 @@ this oracle (tests/test_rnn_gpu.py, tests/test_gru_gpu.py).  First measured maxi
 LAYER_CASES (H in {1, 10, 81, 100, 250, 251, 1024}, T up to 198, B up to 256) 1.8e-7 absolute on h and 3.3e-7 relative L2 on
 dX, dW, dU and db; over every test of this file 1.8e-7 and 9.6e-7 (dU of the H = 1 column-slice case, a gradient of four
 numbers); against the stepped form at H = 250 1.2e-7 and 1.6e-7.  The bounds keep a margin of more than 100x.
+H = 260 (4H = 1040) leaves backward's K a full LDS chunk and a 16-long tail; the scalar paths that only misaligned buffers
+select at H % 4 == 0 are compared bit for bit with the float4 paths.  Both hold the same bounds.
 """
 import ctypes
 import math
@@ -82,11 +84,13 @@ def _oracle(params, x, dh_seq=None, dh_last=None):
 SENTINEL = 12345.5
 
 
-def _run_layer(params, x, dh_seq=None, dh_last=None, wide=1, col=0, stepped=False):
+def _run_layer(params, x, dh_seq=None, dh_last=None, wide=1, col=0, stepped=False, misalign=False):
     """the recurrence through the C ABI.  wide / col: hseq and dh_seq rows are wide * dirs*H floats, the layer at column
     offset col, every other column pre-filled with SENTINEL (and checked afterwards).  stepped: lidbox_lstm_fwd / _bwd
-    (dense strides only) instead of the fused step.  Returns h [B, T, dirs*H], dZ [dirs, B, T, 4H], hseq's slice
+    (dense strides only) instead of the fused step.  misalign: U of every direction and zg are not 16-byte aligned, which
+    selects the scalar load paths whatever H is.  Returns h [B, T, dirs*H], dZ [dirs, B, T, 4H], hseq's slice
     [B, T+2, dirs*H]."""
+    from lidbox_amd.testutil import device_copy
     nv = _nv()
     B, T, C = x.shape
     dirs = len(params)
@@ -95,11 +99,11 @@ def _run_layer(params, x, dh_seq=None, dh_last=None, wide=1, col=0, stepped=Fals
     rs = wide * D
     dev = torch.device("cuda")
     zg = np.stack([(x.astype(np.float64) @ W.astype(np.float64) + b).astype(np.float32) for W, _, b in params])
-    zg_d = torch.from_numpy(zg).to(dev).contiguous()
+    zg_d = device_copy(zg, misalign)
     hbuf = torch.full((B, T + 2, rs), SENTINEL, dtype=torch.float32, device=dev)
     hbuf[:, :, col:col + D] = 0.0
     cseq = torch.zeros((dirs, B, T, H), dtype=torch.float32, device=dev)
-    Us = [torch.from_numpy(U).to(dev) for _, U, _ in params]
+    Us = [device_copy(U, misalign) for _, U, _ in params]
     U1 = nv.ptr(Us[1]) if dirs == 2 else None
     st = nv.current_stream()
     dbuf = None
@@ -168,7 +172,8 @@ def _check(params, x, h, dz, hseq, y, dx_ref, g_ref, tag):
 
 
 LAYER_CASES = [(H, dirs, B, T) for H in (1, 10, 81, 100, 250, 251) for dirs in (1, 2) for (B, T) in ((1, 1), (37, 198))] + \
-              [(250, 2, 256, 198), (1024, 2, 3, 12)]
+              [(250, 2, 256, 198), (1024, 2, 3, 12),
+               (260, 2, 3, 3)]     # backward chunks of 1024 columns: 4H = 1024 + 16
 
 
 @pytest.mark.parametrize("H,dirs,B,T", LAYER_CASES)
@@ -198,6 +203,22 @@ def test_lstm_step_layer_in_a_column_slice(H, dirs, B, T):
     # the strides change where values live, not the values (every load path feeds the MFMAs in the same k order)
     h2, dz2, _ = _run_layer(params, x, dh_seq=dh_seq)
     assert np.array_equal(h, h2) and np.array_equal(dz, dz2)
+
+
+@pytest.mark.parametrize("H,dirs,B,T", [(12, 2, 5, 4), (260, 2, 3, 3)])
+def test_lstm_step_scalar_paths_of_misaligned_buffers_give_the_same_bits(H, dirs, B, T):
+    """H % 4 == 0 takes the float4 kernels unless a buffer is not 16-byte aligned (backward's float4 path depends on the
+    pointers alone): every load path feeds the MFMAs in the same k order, so every output is bit-identical"""
+    rng = np.random.default_rng(H * 1000 + dirs * 100 + B)
+    C = 7
+    params = _params(rng, C, H, dirs)
+    x = rng.standard_normal((B, T, C)).astype(np.float32)
+    dh_seq = rng.standard_normal((B, T, dirs * H)).astype(np.float32)
+    h, dz, hseq = _run_layer(params, x, dh_seq=dh_seq)
+    h2, dz2, hseq2 = _run_layer(params, x, dh_seq=dh_seq, misalign=True)
+    assert np.array_equal(h, h2) and np.array_equal(dz, dz2) and np.array_equal(hseq, hseq2)
+    y, dx_ref, g_ref = _oracle(params, x, dh_seq=dh_seq)
+    _check(params, x, h, dz, hseq, y, dx_ref, g_ref, "aligned H=%d dirs=%d B=%d T=%d" % (H, dirs, B, T))
 
 
 @pytest.mark.parametrize("dirs", [1, 2])
