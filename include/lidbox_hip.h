@@ -909,6 +909,41 @@ int lidbox_bn_relu_dropout_bwd(const float* x, long R, int C, const float* scale
                                unsigned long long seed, const void* step_counter, const float* dy, float* dx,
                                lidbox_stream_t stream);
 
+/* ------------------------------------------------------------------ embedding back-end (lidbox/embed/sklearn_utils.py)
+ * The scoring pass of predict_with_trained_classifier (sklearn_utils.py:230-244) as ONE launch per block of 64 rows:
+ *     u   = (x - mu) . P + q              x [N, D] (row stride ldx); mu [D]; P [D, R] dense row-major; q [R]
+ *     v   = u / ||u||_2                   with LIDBOX_BACKEND_L2; a row with ||u|| = 0 stays 0 (sklearn.preprocessing.normalize)
+ *     s_c = c0[c] - 1/2 sum_r (v_r - theta[c,r])^2 w[c,r]          theta, w [K, R] dense; c0 [K]
+ *     out = max(log_softmax(s), -100)     with LIDBOX_BACKEND_NORMALISED, else out = s
+ * mu is subtracted as x is loaded (never folded into q: embeddings with |mean| >> std would cancel in fp32); a scaler's
+ * 1 / scale belongs in P.  mu and q may be NULL (zeros).  The product runs on the fp32 MFMA pipe; u never leaves the chip.
+ * Outputs: v [N, R] (row stride ldv) and out [N, K] (row stride ldo); either may be NULL, not both.  theta == NULL (then
+ * w == c0 == NULL): only the transform runs and out is ignored.
+ * LIDBOX_BACKEND_LINEAR: "scores are u" -- the class stage is s_c = v_c (K == R, theta == w == c0 == NULL), which makes
+ * the launch a linear classifier: P = coef^T, q = intercept (LinearDiscriminantAnalysis.predict_log_proba with
+ * LIDBOX_BACKEND_NORMALISED).
+ * Limits: 1 <= D <= 4096, 1 <= R <= 255, 1 <= K <= 256, 0 <= N <= LIDBOX_BACKEND_MAX_ROWS per call (the host layer splits
+ * longer inputs); N == 0 is a no-op.  Rows are independent and every sum has a fixed order: a row's outputs are
+ * bit-identical whatever N, the row's position or the run, and whether x takes the 16-byte loads (x 16-byte aligned, ldx
+ * a multiple of 4) or the scalar ones.  A NaN or Inf anywhere in a row of x -- or a ||u||^2 beyond fp32 -- makes all of
+ * that row's outputs NaN and touches no other row. */
+#define LIDBOX_BACKEND_L2          1
+#define LIDBOX_BACKEND_NORMALISED  2
+#define LIDBOX_BACKEND_LINEAR      4
+#define LIDBOX_BACKEND_MAX_ROWS    (1L << 22)
+int lidbox_backend_score(const float* x, long N, int D, long ldx, const float* mu, const float* P, const float* q, int R,
+                         const float* theta, const float* w, const float* c0, int K, int flags, float* v, long ldv,
+                         float* out, long ldo, lidbox_stream_t stream);
+/* The centring pass of the fits (StandardScaler.transform, within-class scatter, GaussianNB variances):
+ *     out[i, :] = (x[i, :] - mu) * inv_scale - cm[seg(i), :]          squared elementwise when square != 0
+ * mu, inv_scale [D] and cm [num_segments, D] may each be NULL (term skipped).  Rows are contiguous by segment: seg(i) = s
+ * with segment_offsets[s] <= i < segment_offsets[s+1] (int64, device, num_segments + 1 entries; only read when cm is
+ * given).  x and out have row strides ldx / ldo and must not overlap.  16-byte accesses when D, the strides and
+ * every pointer allow, scalar ones otherwise (same arithmetic). */
+int lidbox_backend_center_rows(const float* x, long N, int D, long ldx, const float* mu, const float* inv_scale,
+                               const float* cm, const int64_t* segment_offsets, int num_segments, int square, float* out,
+                               long ldo, lidbox_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ FEAT_SPECTROGRAM, FEAT_MEL, FEAT_LOGMEL, FEAT_MFCC = 0, 1, 2, 3
 SRC_F32, SRC_PCM16 = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_RELU_MASK, EPI_ACCUM, EPI_ACCUM_RELU_MASK, EPI_ACCUM_RELU, EPI_RELU = range(8)
 EPI_MASK_BF16 = 0x100            # flag for lidbox_gemm_bf16s_nt: the ReLU-mask source is bfloat16 data
+BACKEND_L2, BACKEND_NORMALISED, BACKEND_LINEAR = 1, 2, 4       # lidbox_backend_score flags
+BACKEND_MAX_ROWS = 1 << 22
 
 
 class LidboxHipError(RuntimeError):
@@ -230,6 +232,8 @@ _SIGS = {
     "lidbox_mla_attention_bwd": (_i, [_vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp]),
     "lidbox_bn_relu_dropout_fwd": (_i, [_vp, _l, _i, _vp, _vp, _f, C.c_ulonglong, _vp, _vp, _vp]),
     "lidbox_bn_relu_dropout_bwd": (_i, [_vp, _l, _i, _vp, _vp, _f, C.c_ulonglong, _vp, _vp, _vp, _vp]),
+    "lidbox_backend_score": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _l, _vp]),
+    "lidbox_backend_center_rows": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():
