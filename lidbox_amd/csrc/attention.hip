@@ -26,7 +26,7 @@ __device__ __forceinline__ void build_bin_table(unsigned short* s_bin, int C, in
 // rows x C, 4 waves per workgroup, grid-stride over rows
 __global__ __launch_bounds__(256) void freq_attention_fwd_kernel(const float* __restrict__ H,
                                                                  const float* logits, long rows, int C,
-                                                                 int d_f, float* F_out,
+                                                                 int d_f, bool vec, float* F_out,
                                                                  float* __restrict__ Hw) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* s_F = reinterpret_cast<float*>(smem);                               // [4][64]
@@ -34,7 +34,6 @@ __global__ __launch_bounds__(256) void freq_attention_fwd_kernel(const float* __
     build_bin_table(s_bin, C, C / d_f);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* wF = s_F + wave * MAX_BINS;
-    const bool vec = (C & 3) == 0;
     for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
         const float z = lane < d_f ? logits[row * d_f + lane] : -FLT_MAX;
         const float m = wave_max(z);
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(256) void freq_attention_fwd_kernel(const float* __
 __global__ __launch_bounds__(256) void freq_attention_bwd_kernel(const float* __restrict__ H,
                                                                  const float* __restrict__ F,
                                                                  const float* __restrict__ dHw, long rows, int C,
-                                                                 int d_f, int relu_mask,
+                                                                 int d_f, int relu_mask, bool vec,
                                                                  float* __restrict__ dlogits,
                                                                  float* __restrict__ dH) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -79,7 +78,6 @@ __global__ __launch_bounds__(256) void freq_attention_bwd_kernel(const float* __
     float* wF = s_F + wave * MAX_BINS;
     float* wH = s_rows + (long)wave * 2 * C;
     float* wD = wH + C;
-    const bool vec = (C & 3) == 0;
     for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
         const float* h = H + row * C;
         const float* d = dHw + row * C;
@@ -120,6 +118,9 @@ int check_attention(const char* fn, long rows, int C, int d_f) {
     return LIDBOX_OK;
 }
 
+// 16-byte row loads and stores: every row starts C floats after the previous one, so C % 4 == 0 and 16-byte aligned bases
+bool rows_vec(int C, const void* a, const void* b) { return C % 4 == 0 && ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0; }
+
 unsigned rows_grid(long rows) {
     long g = lbx_cdiv(rows, 4);
     if (g > 256 * 8) g = 256 * 8;
@@ -135,7 +136,7 @@ extern "C" int lidbox_freq_attention_fwd(const float* H, const float* logits, lo
     if (rows == 0) return LIDBOX_OK;
     const size_t lds = 4 * MAX_BINS * 4 + (size_t)C * 2;
     hipLaunchKernelGGL(freq_attention_fwd_kernel, dim3(rows_grid(rows)), dim3(256), lds, (hipStream_t)stream, H,
-                       logits, rows, C, d_f, F_out, Hw);
+                       logits, rows, C, d_f, rows_vec(C, H, Hw), F_out, Hw);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }
@@ -154,7 +155,7 @@ extern "C" int lidbox_freq_attention_bwd(const float* H, const float* F, const f
         LBX_HIP(raised);
     }
     hipLaunchKernelGGL(freq_attention_bwd_kernel, dim3(rows_grid(rows)), dim3(256), lds, (hipStream_t)stream, H, F,
-                       dHw, rows, C, d_f, relu_mask, dlogits, dH);
+                       dHw, rows, C, d_f, relu_mask, rows_vec(C, H, dHw), dlogits, dH);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

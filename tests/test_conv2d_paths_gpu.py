@@ -31,14 +31,13 @@ import numpy as np
 import pytest
 import torch
 
+from guarded import Guarded
 from oracle import conv2d_np as co
 
 pytestmark = pytest.mark.gpu
 
 REL = 1e-5
 KINDS = ("normal", "offset")
-GUARD = 64                      # words before and after every output / workspace (256 bytes: keeps 16-byte alignment)
-NAN_BITS = 0x7FC00000           # torch.full(..., nan)
 
 # ---------------------------------------------------------------------------------------------------- PATHS: stride 1
 # (B, T, F, k, C_in, C_out).  M = B T F pixels, K = k k C_in, BN = conv_tile_n(C_out) (forward) / conv_tile_n(C_in) (dgrad)
@@ -143,36 +142,6 @@ def _rel(a, b):
 
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-class Guarded:
-    """`shape` elements inside a larger buffer; everything starts as NaN (0xA5 bytes for uint8)"""
-
-    def __init__(self, shape, dtype=torch.float32, init=None):
-        n = int(np.prod(shape))
-        if dtype == torch.uint8:
-            self.buf = torch.full((n + 8 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-            self.view = self.buf[4 * GUARD:4 * GUARD + n].view(shape)
-        else:
-            self.buf = torch.full((n + 2 * GUARD,), float("nan"), dtype=torch.float32, device="cuda")
-            self.view = self.buf[GUARD:GUARD + n].view(shape)
-        if init is not None:
-            self.view.copy_(init)
-        self.n = n
-
-    @property
-    def ptr(self):
-        return ctypes.c_void_p(self.view.data_ptr())
-
-    def numpy(self):
-        """the payload, after checking that the words around it are untouched"""
-        if self.buf.dtype == torch.uint8:
-            lo, hi, want = self.buf[:4 * GUARD], self.buf[4 * GUARD + self.n:], 0xA5
-        else:
-            ints = self.buf.view(torch.int32)
-            lo, hi, want = ints[:GUARD], ints[GUARD + self.n:], NAN_BITS
-        assert hi.numel() == lo.numel() and bool((lo == want).all()) and bool((hi == want).all()), "guard words overwritten"
-        return self.view.cpu().numpy()
 
 
 def _workspace(nbytes):
