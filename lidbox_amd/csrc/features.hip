@@ -845,12 +845,14 @@ __global__ __launch_bounds__(256, FEAT_WAVES) void fused_feat512_kernel(const Fu
         //         four zeros instead.
         float2 za[16], zb[16];
         // Interior tiles (every read of the tile's 8 frames, up to sample 511 of the last one, stays inside the
-        // utterance -- wave-uniform test; 24 of 25 tiles at 2 s): one base address per lane and immediate offsets,
-        // no per-load address selects and no window guards: the samples after a frame are the utterance's own
-        // later samples and the window table is zero there.  The guarded path below handles an utterance's last tile.
+        // samples the utterance's frames own, [0, (T - 1) S + L) -- wave-uniform test; 24 of 25 tiles at 2 s): one
+        // base address per lane and immediate offsets, no per-load address selects and no window guards: the samples
+        // after a frame are a later frame's own samples and the window table is zero there.  The guarded path below
+        // handles an utterance's last tile(s); it never reads behind a frame, so a NaN / Inf in the tail that no frame
+        // owns (tf.signal.frame drops it) cannot reach the arithmetic as NaN * 0.
         // (Round 2 also measured skipping the always-zero samples 416..511 of frames <= 416 samples behind a wave-uniform branch:
         // slower for log-mel, 28.7 vs 28.0 us at B = 256, neutral for MFCC; removed.)
-        const bool interior = VEC4 && (long)(t0 + 7) * a.S + 512 <= a.N;
+        const bool interior = VEC4 && (long)(t0 + 7) * a.S + 512 <= (long)(a.T - 1) * a.S + a.L;
         if (interior) {
             const float* base = src + 4 * q;
 #pragma unroll
@@ -1015,7 +1017,11 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
     const unsigned tile0 = chunk * (unsigned)a.tiles_per_wg;
     const unsigned ntl = min((unsigned)a.tiles_per_wg, (unsigned)a.ntiles - tile0);     // tiles of this workgroup
     const unsigned tpu = (unsigned)a.tiles_per_utt;
-    const unsigned utt_bytes = ((unsigned)a.N & ~3u) * ESZ;             // a float4 / short4 at a multiple of 4 samples is wholly inside or wholly outside
+    // The descriptor ends with the utterance's LAST FRAME, (T - 1) S + L <= N (a multiple of 4: S and L are), not with the utterance: the
+    // 32 NL samples a lane group loads for the last frames reach past it into samples no frame owns, whose zero window weight would turn a
+    // NaN / Inf there into a NaN frame (tf.signal.frame never reads them).  A float4 / short4 at a multiple of 4 samples is wholly inside
+    // or wholly outside.
+    const unsigned utt_bytes = (unsigned)(((long)(a.T - 1) * a.S + a.L) * ESZ);
 
     // sample loads of local tile `local` (wave-uniform; past the workgroup's last tile: a descriptor of zero records, no traffic)
     xreg_t x[NL];                                          // NL = 13: frames of <= 416 samples, the window table is zero behind them

@@ -465,7 +465,10 @@ def test_pcm16_source_read_in_place_is_bit_identical_to_convert_then_extract(kin
 def test_nonfinite_flag_from_the_store_stage():
     """tf.debugging.assert_all_finite of reference tf_utils.py:173-194 without a pass over the output: the kernels fold "a value
     I stored is not finite" into a 4-byte flag.  Clean signals leave it 0; one NaN / Inf sample anywhere inside a frame sets it and
-    extract_features raises like the reference; a poisoned sample that no frame reads (the tail behind the last frame) does not."""
+    extract_features raises like the reference; a poisoned sample that no frame owns does not: the tail behind the last frame, of
+    which this test plants sample 16 050 (behind every load); the zero-weighted samples 15 920 .. 15 935 right behind the last frame,
+    which the last frame's lanes would load, are planted by tests/test_features_paths_gpu.py (the kernels bound their loads at
+    (T - 1) S + L since then)."""
     from lidbox_amd import _native as nv
     from lidbox_amd.data import tf_utils
     from lidbox_amd.features import audio
