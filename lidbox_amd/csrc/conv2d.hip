@@ -25,6 +25,12 @@
 // tile to the workspace, workgroups of the first kidx tile also the partial column sums of dY (the bias gradient), and a
 // second launch sums the partials in a fixed order.  No atomics: bit-identical from run to run.
 //
+// The stride-1 kernels and the strided ones further down (clstm's Conv2D) are one tile program: tile_clear, tile_pipeline
+// (register-to-LDS staging and the double-buffered main loop), tile_walk (the 16x16 C/D map with the element store as a
+// callable), wgrad_chunks (pipeline + bias column sums) and wgrad_store (partial tile + bias row) stand once; a kernel keeps
+// its geometry, its row / tap decomposition and its load.  On the host with_tile_n turns the tile width into a template
+// argument for all four launches and run_wgrad is the body of both wgrad entry points.
+//
 // BN-apply + MaxPool2D: one pass reads the conv output, applies the BatchNormalization scale / shift (gamma may be
 // negative, so normalisation comes first) and takes the 2 x 2 maximum ("valid": an odd last row / column is dropped).
 // Ties go to the FIRST maximum in the reference image's scan order -- lower frequency row first, then lower time column
@@ -32,6 +38,8 @@
 // which gathers: each input cell takes its window's gradient when it is the recorded winner, zero otherwise (and zero for
 // the dropped cells).
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -89,16 +97,125 @@ __device__ __forceinline__ void mma_lds_chunk(f32x4 (&acc)[2][BN / 16], const fl
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the tile pipeline
+// One program for the four tile kernels below: a workgroup of 256 threads owns a 128 x BN tile, walks its contraction
+// [lo, hi) in chunks of CV_KC through As [CV_KC][CV_LDA] and Bs [CV_KC][cv_ldb] and holds the next chunk in registers
+// (av, bv) while the current one feeds the MFMAs.  A kernel brings its geometry and `load(c)`, which fills av and bv for the
+// chunk at c (zeros outside the tile, the image or the contraction), and names the A layout that its load produces:
+//     A_ROWS  thread (kk = tid & 15, r0 = tid >> 4) holds A[row r0 + 16 j][k kk]       (forward, dgrad: k is innermost in x)
+//     A_KIDX  thread (kk = tid & 127, p0 = tid >> 7) holds A[row kk][k p0 + 2 j]       (wgrad: the row is innermost in x)
+// B is the same in all four: element e = tid + 256 q of the chunk's [CV_KC][BN] block.
+// Source forms that the compiled code depends on (docs/LAB_NOTEBOOK.md section 19): the kernel issues the first load itself
+// and hands down its own tid, w and lane; tile_walk gets its row and column bases, and the store it calls captures by value,
+// never a reference to a kernel argument.
+enum ALayout { A_ROWS, A_KIDX };
+
+template <ALayout L>
+__device__ __forceinline__ void tile_stage_a(float (&As)[CV_KC * CV_LDA], const float (&av)[8], int tid) {
+    if (L == A_ROWS) {
+        const int kk = tid & 15, r0 = tid >> 4;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[kk * CV_LDA + r0 + 16 * j] = av[j];
+    } else {
+        const int kk = tid & 127, p0 = tid >> 7;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[(p0 + 2 * j) * CV_LDA + kk] = av[j];
+    }
+}
+
+template <int BN>
+__device__ __forceinline__ void tile_stage_b(float (&Bs)[CV_KC * cv_ldb<BN>()], const float (&bv)[CV_KC * BN / 256], int tid) {
+#pragma unroll
+    for (int q = 0; q < CV_KC * BN / 256; ++q) {
+        const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+        Bs[kr * cv_ldb<BN>() + n] = bv[q];
+    }
+}
+
+template <int BN>
+__device__ __forceinline__ void tile_clear(f32x4 (&acc)[2][BN / 16]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+struct NoChunkHook {
+    __device__ __forceinline__ void operator()(const float*) const {}
+};
+
+// acc += the chunks of [lo, hi) (I: int or long, the type load takes).  The caller has called load(lo) when the range is not
+// empty.  hook(Bs) runs once per chunk between the prefetch of the next chunk and the MFMAs, with the current chunk in
+// LDS: wgrad sums dY's columns there.
+template <int BN, ALayout L, typename I, typename Load, typename Hook = NoChunkHook>
+__device__ __forceinline__ void tile_pipeline(f32x4 (&acc)[2][BN / 16], const float (&av)[8],
+                                              const float (&bv)[CV_KC * BN / 256], int tid, int w, int lane, I lo, I hi,
+                                              const Load& load, const Hook& hook = Hook()) {
+    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * cv_ldb<BN>()];
+    for (I c = lo; c < hi; c += CV_KC) {
+        __syncthreads();                                  // the previous chunk's LDS reads are done
+        tile_stage_a<L>(As, av, tid);
+        tile_stage_b<BN>(Bs, bv, tid);
+        __syncthreads();
+        if (c + CV_KC < hi) load(c + CV_KC);
+        hook(Bs);
+        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
+    }
+}
+
+// The 16x16 C/D map of the tile at (row0, col0): lane (c, q4) of wave w holds column col0 + 16 j + c of rows row0 + w * 32 +
+// 16 i + 4 q4 + r.  store(row, col, v, t) gets each element with its place (row in R, int or long) and t = colv[col], the
+// kernel's per-column term (the bias), or 0 when colv is NULL.
+template <int BN, typename R, typename Store>
+__device__ __forceinline__ void tile_walk(const f32x4 (&acc)[2][BN / 16], int w, int lane, R row0, int col0,
+                                          const float* __restrict__ colv, const Store& store) {
+    const int c = lane & 15, q4 = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < BN / 16; ++j) {
+        const int n = col0 + 16 * j + c;
+        const float t = colv ? colv[n] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) store(row0 + w * 32 + 16 * i + 4 * q4 + r, n, acc[i][j][r], t);
+    }
+}
+
+// wgrad, both families, grid (ceil(K / 128), Cout / BN, P): rows are kidx, the contraction runs over the pixels [mlo, mhi)
+// of partition p = blockIdx.z.  Workgroups of the first kidx tile also sum dY's columns (the bias gradient) from the B chunk
+// in LDS, one thread per column and chunk rows in order.
+template <int BN, typename Load>
+__device__ __forceinline__ void wgrad_chunks(f32x4 (&acc)[2][BN / 16], float& dbacc, const float (&av)[8],
+                                             const float (&bv)[CV_KC * BN / 256], int tid, int w, int lane, long mlo, long mhi,
+                                             const Load& load) {
+    const bool bias_tile = blockIdx.x == 0;
+    tile_pipeline<BN, A_KIDX>(acc, av, bv, tid, w, lane, mlo, mhi, load, [&dbacc, bias_tile, tid](const float* Bs) {
+        if (bias_tile && tid < BN) {
+#pragma unroll
+            for (int pr = 0; pr < CV_KC; ++pr) dbacc += Bs[pr * cv_ldb<BN>() + tid];
+        }
+    });
+}
+
+// part[kidx][co][p] = the partial tile (rows < K), dbpart[co][p] = the partial column sums
+template <int BN>
+__device__ __forceinline__ void wgrad_store(const f32x4 (&acc)[2][BN / 16], float dbacc, int tid, int w, int lane,
+                                            float* __restrict__ part, float* __restrict__ dbpart, int K, int Cout, int P) {
+    const int k0 = blockIdx.x * CV_BM, n0 = blockIdx.y * BN, p = blockIdx.z;
+    tile_walk<BN>(acc, w, lane, k0, n0, nullptr, [=](int kr, int n, float v, float) {
+        if (kr < K) part[((long)kr * Cout + n) * P + p] = v;
+    });
+    if (blockIdx.x == 0 && tid < BN) dbpart[(long)(n0 + tid) * P + p] = dbacc;
+}
+
 // ---------------------------------------------------------------------------------------------- forward (and dgrad)
 // grid (ceil(M / 128), Cout / BN); thread (kk = tid & 15, r0 = tid >> 4) loads A[r0 + 16 j][kk], j < 8
 template <int BN>
 __global__ __launch_bounds__(256) void conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                        const float* __restrict__ bias, int relu, float* __restrict__ y,
                                                        const ConvGeom g) {
-    constexpr int LDB = cv_ldb<BN>();
     constexpr int BQ = CV_KC * BN / 256;      // B-operand loads per thread and chunk (1, 2 or 4)
-    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
-    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const long m0 = (long)blockIdx.x * CV_BM;
     const int n0 = blockIdx.y * BN;
@@ -129,41 +246,15 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const float* __restrict__
         }
     };
     f32x4 acc[2][BN / 16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    tile_clear<BN>(acc);
     load(0);
-    for (int kc = 0; kc < g.K; kc += CV_KC) {
-        __syncthreads();                                  // the previous chunk's LDS reads are done
-#pragma unroll
-        for (int j = 0; j < 8; ++j) As[kk * CV_LDA + r0 + 16 * j] = av[j];
-#pragma unroll
-        for (int q = 0; q < BQ; ++q) {
-            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
-            Bs[kr * LDB + n] = bv[q];
-        }
-        __syncthreads();
-        if (kc + CV_KC < g.K) load(kc + CV_KC);
-        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
-    }
-    // epilogue: lane (c, q) holds column 16 j + c of rows 16 i + 4 q + r (the 16x16 C/D map)
-    const int c = lane & 15, q4 = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < BN / 16; ++j) {
-        const int n = n0 + 16 * j + c;
-        const float bb = bias ? bias[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long m = m0 + w * 32 + 16 * i + 4 * q4 + r;
-                if (m >= g.M) continue;
-                float v = acc[i][j][r] + bb;
-                if (relu) v = fmaxf(v, 0.0f);
-                y[m * g.Cout + n] = v;
-            }
-    }
+    tile_pipeline<BN, A_ROWS>(acc, av, bv, tid, w, lane, 0, g.K, load);
+    tile_walk<BN>(acc, w, lane, m0, n0, bias, [y, relu, M = g.M, Cout = g.Cout](long m, int n, float v, float bb) {
+        if (m >= M) return;
+        v += bb;
+        if (relu) v = fmaxf(v, 0.0f);
+        y[m * Cout + n] = v;
+    });
 }
 
 // Wd[kh'][kw'][co][ci] = W[k-1-kh'][k-1-kw'][ci][co]: the kernel of the transposed convolution
@@ -187,16 +278,12 @@ template <int BN>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                          float* __restrict__ part, float* __restrict__ dbpart, long per,
                                                          int P, const ConvGeom g) {
-    constexpr int LDB = cv_ldb<BN>();
     constexpr int BQ = CV_KC * BN / 256;
-    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
-    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int k0 = blockIdx.x * CV_BM, n0 = blockIdx.y * BN, p = blockIdx.z;
     const long mlo = (long)p * per, mhi = min(g.M, mlo + per);
     const int kk = tid & 127, p0 = tid >> 7;
     const KTap tp = ktap(g, k0 + kk);
-    const bool bias_tile = blockIdx.x == 0;
     float av[8], bv[BQ];
     auto load = [&](long mc) {
         // (t, f) of pixel mc + p0, then stepped by 2 pixels
@@ -221,42 +308,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
         }
     };
     f32x4 acc[2][BN / 16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dbacc = 0.0f;
+    tile_clear<BN>(acc);
     if (mlo < mhi) load(mlo);
-    for (long mc = mlo; mc < mhi; mc += CV_KC) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) As[(p0 + 2 * j) * CV_LDA + kk] = av[j];
-#pragma unroll
-        for (int q = 0; q < BQ; ++q) {
-            const int e = tid + 256 * q, pr = e / BN, n = e - pr * BN;
-            Bs[pr * LDB + n] = bv[q];
-        }
-        __syncthreads();
-        if (mc + CV_KC < mhi) load(mc + CV_KC);
-        if (bias_tile && tid < BN) {
-#pragma unroll
-            for (int pr = 0; pr < CV_KC; ++pr) dbacc += Bs[pr * LDB + tid];
-        }
-        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
-    }
-    const int c = lane & 15, q4 = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < BN / 16; ++j) {
-        const int n = n0 + 16 * j + c;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kr = k0 + w * 32 + 16 * i + 4 * q4 + r;
-                if (kr < g.K) part[((long)kr * g.Cout + n) * P + p] = acc[i][j][r];
-            }
-    }
-    if (bias_tile && tid < BN) dbpart[(long)(n0 + tid) * P + p] = dbacc;
+    wgrad_chunks<BN>(acc, dbacc, av, bv, tid, w, lane, mlo, mhi, load);
+    wgrad_store<BN>(acc, dbacc, tid, w, lane, part, dbpart, g.K, g.Cout, P);
 }
 
 // dW[i] = sum_p part[i][p] (i < K * Cout), db[co] = sum_p dbpart[co][p], in a fixed order.  Few partitions (P < 64): one
@@ -407,15 +463,21 @@ ConvGeom geom(int B, int T, int F, int Cin, int Cout, int ks) {
 
 int conv_tile_n(int Cout) { return Cout % 64 == 0 ? 64 : Cout % 32 == 0 ? 32 : 16; }
 
+// f(std::integral_constant<int, bn>): the one place that turns conv_tile_n's value into a template argument
+template <typename F>
+void with_tile_n(int bn, F&& f) {
+    if (bn == 64)
+        f(std::integral_constant<int, 64>());
+    else if (bn == 32)
+        f(std::integral_constant<int, 32>());
+    else
+        f(std::integral_constant<int, 16>());
+}
+
 int launch_fwd(const float* x, const float* W, const float* bias, int relu, float* y, const ConvGeom& g, hipStream_t st) {
     const int bn = conv_tile_n(g.Cout);
     const dim3 grid((unsigned)lbx_cdiv(g.M, CV_BM), (unsigned)(g.Cout / bn));
-    if (bn == 64)
-        hipLaunchKernelGGL(conv_fwd_kernel<64>, grid, dim3(256), 0, st, x, W, bias, relu, y, g);
-    else if (bn == 32)
-        hipLaunchKernelGGL(conv_fwd_kernel<32>, grid, dim3(256), 0, st, x, W, bias, relu, y, g);
-    else
-        hipLaunchKernelGGL(conv_fwd_kernel<16>, grid, dim3(256), 0, st, x, W, bias, relu, y, g);
+    with_tile_n(bn, [&](auto BN) { hipLaunchKernelGGL(conv_fwd_kernel<BN()>, grid, dim3(256), 0, st, x, W, bias, relu, y, g); });
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }
@@ -432,7 +494,48 @@ void wgrad_plan_kmn(long K, long M, int Cout, int* P, long* per) {
     *P = (int)p;
 }
 
-void wgrad_plan(const ConvGeom& g, int* P, long* per) { wgrad_plan_kmn(g.K, g.M, g.Cout, P, per); }
+// P partial tiles [K][Cout] and P partial bias rows [Cout]
+size_t wgrad_workspace_bytes(long K, long M, int Cout) {
+    int P;
+    long per;
+    wgrad_plan_kmn(K, M, Cout, &P, &per);
+    return (size_t)P * ((size_t)K * Cout + Cout) * sizeof(float);
+}
+
+// Both wgrad entry points after their argument checks: dW [K][Cout] and db [Cout] (may be NULL) from M pixels.
+// launch(BN, grid, part, dbpart, per, P) starts the family's tile kernel; the reduce kernels are shared.
+template <typename Launch>
+int run_wgrad(const char* fn, long K, long M, int Cout, float* dW, float* db, void* workspace, size_t workspace_bytes,
+              hipStream_t st, Launch&& launch) {
+    const long nw = K * Cout;
+    if (M == 0) {
+        LBX_HIP(hipMemsetAsync(dW, 0, nw * sizeof(float), st));
+        if (db) LBX_HIP(hipMemsetAsync(db, 0, Cout * sizeof(float), st));
+        return LIDBOX_OK;
+    }
+    if (!(workspace && workspace_bytes >= wgrad_workspace_bytes(K, M, Cout) && ((uintptr_t)workspace & 15) == 0)) {
+        lidbox_set_error("%s: invalid argument: workspace >= %s_workspace() bytes, 16-byte aligned", fn, fn);
+        return LIDBOX_E_INVALID;
+    }
+    int P;
+    long per;
+    wgrad_plan_kmn(K, M, Cout, &P, &per);
+    float* part = (float*)workspace;
+    float* dbpart = part + (long)P * nw;
+    const int bn = conv_tile_n(Cout);
+    const dim3 grid((unsigned)lbx_cdiv(K, CV_BM), (unsigned)(Cout / bn), (unsigned)P);
+    with_tile_n(bn, [&](auto BN) { launch(BN, grid, part, dbpart, per, P); });
+    LBX_LAUNCH_OK();
+    const long nout = nw + (db ? Cout : 0);
+    if (P >= 64)
+        hipLaunchKernelGGL(conv_wgrad_reduce_wide_kernel, dim3((unsigned)lbx_cdiv(nout, 4)), dim3(256), 0, st, part, dbpart, P, nw,
+                           nout, dW, db);
+    else
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)lbx_cdiv(nout, 256)), dim3(256), 0, st, part, dbpart, P, nw, nout,
+                           dW, db);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
 
 // ============================================================================================== strided, rectangular Conv2D
 // lidbox/models/clstm.py:51-60: Conv2D(C_out, (kt, kf), strides=(1, sf), padding="same") on the time-major image
@@ -463,10 +566,7 @@ __device__ __forceinline__ int sg_tap(const SGeom& g, int i, int j) { return g.t
 template <int BN, bool DG>
 __global__ __launch_bounds__(256) void sconv_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                     const float* __restrict__ bias, float* __restrict__ y, const SGeom g) {
-    constexpr int LDB = cv_ldb<BN>();
     constexpr int BQ = CV_KC * BN / 256;
-    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
-    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int col = blockIdx.y;                      // fo (forward) / f (dgrad)
     const int n0 = blockIdx.z * BN;
@@ -548,39 +648,14 @@ __global__ __launch_bounds__(256) void sconv_kernel(const float* __restrict__ x,
         }
     };
     f32x4 acc[2][BN / 16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    tile_clear<BN>(acc);
     if (Kv > 0) load(0);
-    for (int kc = 0; kc < Kv; kc += CV_KC) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) As[kk * CV_LDA + r0 + 16 * j] = av[j];
-#pragma unroll
-        for (int q = 0; q < BQ; ++q) {
-            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
-            Bs[kr * LDB + n] = bv[q];
-        }
-        __syncthreads();
-        if (kc + CV_KC < Kv) load(kc + CV_KC);
-        mma_lds_chunk<BN>(acc, As, Bs, w, lane);
-    }
-    const int c = lane & 15, q4 = lane >> 4;
+    tile_pipeline<BN, A_ROWS>(acc, av, bv, tid, w, lane, 0, Kv, load);
     const int Fcol = DG ? g.F : g.Fo;
-#pragma unroll
-    for (int j = 0; j < BN / 16; ++j) {
-        const int n = n0 + 16 * j + c;
-        const float bb0 = (!DG && bias) ? bias[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long row = r0t + w * 32 + 16 * i + 4 * q4 + r;
-                if (row >= R) continue;
-                y[(row * Fcol + col) * Ncol + n] = acc[i][j][r] + bb0;      // row = b Rt + t: pixel (b, t, col)
-            }
-    }
+    tile_walk<BN>(acc, w, lane, r0t, n0, DG ? nullptr : bias, [y, R, Fcol, col, Ncol](long row, int n, float v, float bb0) {
+        if (row >= R) return;
+        y[(row * Fcol + col) * Ncol + n] = v + bb0;      // row = b Rt + t: pixel (b, t, col)
+    });
 }
 
 // Wt[tap][co][ci] = W[tap][ci][co]
@@ -601,10 +676,7 @@ template <int BN>
 __global__ __launch_bounds__(256) void sconv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           float* __restrict__ part, float* __restrict__ dbpart, long per,
                                                           int P, const SGeom g) {
-    constexpr int LDB = cv_ldb<BN>();
     constexpr int BQ = CV_KC * BN / 256;
-    __shared__ __attribute__((aligned(16))) float As[CV_KC * CV_LDA];
-    __shared__ __attribute__((aligned(16))) float Bs[CV_KC * LDB];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int k0 = blockIdx.x * CV_BM, n0 = blockIdx.y * BN, p = blockIdx.z;
     const long BTo = (long)g.B * g.To, M = BTo * g.Fo;
@@ -675,44 +747,13 @@ __global__ __launch_bounds__(256) void sconv_wgrad_kernel(const float* __restric
         }
     };
     f32x4 acc[2][BN / 16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < BN / 16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dbacc = 0.0f;
+    tile_clear<BN>(acc);
     if (live) {
         if (mlo < mhi) load(mlo);
-        for (long mc = mlo; mc < mhi; mc += CV_KC) {
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 8; ++j) As[(p0 + 2 * j) * CV_LDA + kk] = av[j];
-#pragma unroll
-            for (int q = 0; q < BQ; ++q) {
-                const int e = tid + 256 * q, pr = e / BN, n = e - pr * BN;
-                Bs[pr * LDB + n] = bv[q];
-            }
-            __syncthreads();
-            if (mc + CV_KC < mhi) load(mc + CV_KC);
-            if (bias_tile && tid < BN) {
-#pragma unroll
-                for (int pr = 0; pr < CV_KC; ++pr) dbacc += Bs[pr * LDB + tid];
-            }
-            mma_lds_chunk<BN>(acc, As, Bs, w, lane);
-        }
+        wgrad_chunks<BN>(acc, dbacc, av, bv, tid, w, lane, mlo, mhi, load);
     }
-    const int c = lane & 15, q4 = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < BN / 16; ++j) {
-        const int n = n0 + 16 * j + c;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kr = k0 + w * 32 + 16 * i + 4 * q4 + r;
-                if (kr < g.K) part[((long)kr * g.Cout + n) * P + p] = acc[i][j][r];
-            }
-    }
-    if (bias_tile && tid < BN) dbpart[(long)(n0 + tid) * P + p] = dbacc;
+    wgrad_store<BN>(acc, dbacc, tid, w, lane, part, dbpart, g.K, g.Cout, P);
 }
 
 // ---------------------------------------------------------------------------------------------- BN-apply + ReLU (+ max over F)
@@ -811,15 +852,13 @@ int launch_sconv(const float* x, const float* W, const float* bias, float* y, co
     const int Ncol = DG ? g.Cin : g.Cout;
     const int bn = conv_tile_n(Ncol);
     const dim3 grid((unsigned)lbx_cdiv((long)g.B * (DG ? g.T : g.To), CV_BM), (unsigned)(DG ? g.F : g.Fo), (unsigned)(Ncol / bn));
-    if (bn == 64)
-        hipLaunchKernelGGL((sconv_kernel<64, DG>), grid, dim3(256), 0, st, x, W, bias, y, g);
-    else if (bn == 32)
-        hipLaunchKernelGGL((sconv_kernel<32, DG>), grid, dim3(256), 0, st, x, W, bias, y, g);
-    else
-        hipLaunchKernelGGL((sconv_kernel<16, DG>), grid, dim3(256), 0, st, x, W, bias, y, g);
+    with_tile_n(bn, [&](auto BN) { hipLaunchKernelGGL((sconv_kernel<BN(), DG>), grid, dim3(256), 0, st, x, W, bias, y, g); });
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }
+
+// the two weight-copy launches (rotate, transpose): grid-stride over nw elements, at most 1024 workgroups
+dim3 wcopy_grid(long nw) { return dim3((unsigned)(lbx_cdiv(nw, 256) < 1024 ? lbx_cdiv(nw, 256) : 1024)); }
 
 int ew_blocks(long n) {
     const long b = lbx_cdiv(n, 256);
@@ -851,8 +890,7 @@ extern "C" int lidbox_conv2d_dgrad(const float* dy, int B, int T, int F, int C_i
     hipStream_t st = (hipStream_t)stream;
     float* Wd = (float*)workspace;
     const long nw = (long)k * k * C_in * C_out;
-    hipLaunchKernelGGL(conv_rot_kernel, dim3((unsigned)(lbx_cdiv(nw, 256) < 1024 ? lbx_cdiv(nw, 256) : 1024)), dim3(256), 0, st,
-                       W, Wd, k, C_in, C_out);
+    hipLaunchKernelGGL(conv_rot_kernel, wcopy_grid(nw), dim3(256), 0, st, W, Wd, k, C_in, C_out);
     LBX_LAUNCH_OK();
     return launch_fwd(dy, Wd, nullptr, 0, dx, geom(B, T, F, C_out, C_in, k), st);
 }
@@ -860,10 +898,7 @@ extern "C" int lidbox_conv2d_dgrad(const float* dy, int B, int T, int F, int C_i
 extern "C" size_t lidbox_conv2d_wgrad_workspace(int B, int T, int F, int C_in, int C_out, int k) {
     if (B < 1 || T < 1 || F < 1 || C_in < 1 || C_out < 16 || C_out % 16 != 0 || k < 1) return 0;
     const ConvGeom g = geom(B, T, F, C_in, C_out, k);
-    int P;
-    long per;
-    wgrad_plan(g, &P, &per);
-    return (size_t)P * ((size_t)g.K * C_out + C_out) * sizeof(float);
+    return wgrad_workspace_bytes(g.K, g.M, C_out);
 }
 
 extern "C" int lidbox_conv2d_wgrad(const float* x, const float* dy, int B, int T, int F, int C_in, int C_out, int k, float* dW,
@@ -872,38 +907,10 @@ extern "C" int lidbox_conv2d_wgrad(const float* x, const float* dy, int B, int T
     LBX_ARG(x && dy && dW, "x, dy, dW != NULL");
     hipStream_t st = (hipStream_t)stream;
     const ConvGeom g = geom(B, T, F, C_in, C_out, k);
-    const long nw = (long)g.K * C_out;
-    if (B == 0) {
-        LBX_HIP(hipMemsetAsync(dW, 0, nw * sizeof(float), st));
-        if (db) LBX_HIP(hipMemsetAsync(db, 0, C_out * sizeof(float), st));
-        return LIDBOX_OK;
-    }
-    LBX_ARG(workspace && workspace_bytes >= lidbox_conv2d_wgrad_workspace(B, T, F, C_in, C_out, k) &&
-                ((uintptr_t)workspace & 15) == 0,
-            "workspace >= lidbox_conv2d_wgrad_workspace() bytes, 16-byte aligned");
-    int P;
-    long per;
-    wgrad_plan(g, &P, &per);
-    float* part = (float*)workspace;
-    float* dbpart = part + (long)P * nw;
-    const int bn = conv_tile_n(C_out);
-    const dim3 grid((unsigned)lbx_cdiv(g.K, CV_BM), (unsigned)(C_out / bn), (unsigned)P);
-    if (bn == 64)
-        hipLaunchKernelGGL(conv_wgrad_kernel<64>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
-    else if (bn == 32)
-        hipLaunchKernelGGL(conv_wgrad_kernel<32>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
-    else
-        hipLaunchKernelGGL(conv_wgrad_kernel<16>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
-    LBX_LAUNCH_OK();
-    const long nout = nw + (db ? C_out : 0);
-    if (P >= 64)
-        hipLaunchKernelGGL(conv_wgrad_reduce_wide_kernel, dim3((unsigned)lbx_cdiv(nout, 4)), dim3(256), 0, st, part, dbpart, P, nw,
-                           nout, dW, db);
-    else
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)lbx_cdiv(nout, 256)), dim3(256), 0, st, part, dbpart, P, nw, nout,
-                           dW, db);
-    LBX_LAUNCH_OK();
-    return LIDBOX_OK;
+    return run_wgrad(__func__, g.K, g.M, C_out, dW, db, workspace, workspace_bytes, st,
+                     [&](auto BN, dim3 grid, float* part, float* dbpart, long per, int P) {
+                         hipLaunchKernelGGL(conv_wgrad_kernel<BN()>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+                     });
 }
 
 extern "C" int lidbox_bn_maxpool2d_fwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift,
@@ -990,8 +997,7 @@ extern "C" int lidbox_conv2d_strided_dgrad(const float* dy, int B, int T, int F,
     hipStream_t st = (hipStream_t)stream;
     float* Wt = (float*)workspace;
     const long nw = (long)taps.kt * taps.kf * C_in * C_out;
-    hipLaunchKernelGGL(sconv_transpose_kernel, dim3((unsigned)(lbx_cdiv(nw, 256) < 1024 ? lbx_cdiv(nw, 256) : 1024)), dim3(256), 0,
-                       st, W, Wt, taps.kt * taps.kf, C_in, C_out);
+    hipLaunchKernelGGL(sconv_transpose_kernel, wcopy_grid(nw), dim3(256), 0, st, W, Wt, taps.kt * taps.kf, C_in, C_out);
     LBX_LAUNCH_OK();
     return launch_sconv<true>(dy, Wt, nullptr, dx, sgeom(B, T, F, C_in, C_out, taps), st);
 }
@@ -999,10 +1005,7 @@ extern "C" int lidbox_conv2d_strided_dgrad(const float* dy, int B, int T, int F,
 extern "C" size_t lidbox_conv2d_strided_wgrad_workspace(int B, int T, int F, int C_in, int C_out, lidbox_conv2d_taps_t taps) {
     if (B < 1 || sconv_check(__func__, B, T, F, C_in, C_out, taps) != LIDBOX_OK) return 0;
     const SGeom g = sgeom(B, T, F, C_in, C_out, taps);
-    int P;
-    long per;
-    wgrad_plan_kmn(g.K, (long)B * g.To * g.Fo, C_out, &P, &per);
-    return (size_t)P * ((size_t)g.K * C_out + C_out) * sizeof(float);
+    return wgrad_workspace_bytes(g.K, (long)B * g.To * g.Fo, C_out);
 }
 
 extern "C" int lidbox_conv2d_strided_wgrad(const float* x, const float* dy, int B, int T, int F, int C_in, int C_out,
@@ -1012,38 +1015,10 @@ extern "C" int lidbox_conv2d_strided_wgrad(const float* x, const float* dy, int 
     LBX_ARG(x && dy && dW, "x, dy, dW != NULL");
     hipStream_t st = (hipStream_t)stream;
     const SGeom g = sgeom(B, T, F, C_in, C_out, taps);
-    const long nw = (long)g.K * C_out;
-    if (B == 0) {
-        LBX_HIP(hipMemsetAsync(dW, 0, nw * sizeof(float), st));
-        if (db) LBX_HIP(hipMemsetAsync(db, 0, C_out * sizeof(float), st));
-        return LIDBOX_OK;
-    }
-    LBX_ARG(workspace && workspace_bytes >= lidbox_conv2d_strided_wgrad_workspace(B, T, F, C_in, C_out, taps) &&
-                ((uintptr_t)workspace & 15) == 0,
-            "workspace >= lidbox_conv2d_strided_wgrad_workspace() bytes, 16-byte aligned");
-    int P;
-    long per;
-    wgrad_plan_kmn(g.K, (long)B * g.To * g.Fo, C_out, &P, &per);
-    float* part = (float*)workspace;
-    float* dbpart = part + (long)P * nw;
-    const int bn = conv_tile_n(C_out);
-    const dim3 grid((unsigned)lbx_cdiv(g.K, CV_BM), (unsigned)(C_out / bn), (unsigned)P);
-    if (bn == 64)
-        hipLaunchKernelGGL(sconv_wgrad_kernel<64>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
-    else if (bn == 32)
-        hipLaunchKernelGGL(sconv_wgrad_kernel<32>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
-    else
-        hipLaunchKernelGGL(sconv_wgrad_kernel<16>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
-    LBX_LAUNCH_OK();
-    const long nout = nw + (db ? C_out : 0);
-    if (P >= 64)
-        hipLaunchKernelGGL(conv_wgrad_reduce_wide_kernel, dim3((unsigned)lbx_cdiv(nout, 4)), dim3(256), 0, st, part, dbpart, P, nw,
-                           nout, dW, db);
-    else
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)lbx_cdiv(nout, 256)), dim3(256), 0, st, part, dbpart, P, nw, nout,
-                           dW, db);
-    LBX_LAUNCH_OK();
-    return LIDBOX_OK;
+    return run_wgrad(__func__, g.K, (long)B * g.To * g.Fo, C_out, dW, db, workspace, workspace_bytes, st,
+                     [&](auto BN, dim3 grid, float* part, float* dbpart, long per, int P) {
+                         hipLaunchKernelGGL(sconv_wgrad_kernel<BN()>, grid, dim3(256), 0, st, x, dy, part, dbpart, per, P, g);
+                     });
 }
 
 extern "C" int lidbox_bn_relu_fwd(const float* x, long R, int C, const float* scale, const float* shift, float* y,
