@@ -115,6 +115,34 @@ int lidbox_extract_features_fwd_ex(const lidbox_feat_plan* plan, int kind, const
 int lidbox_extract_features_fwd_pcm16(const lidbox_feat_plan* plan, int kind, const int16_t* pcm, int B, int N, long sig_stride,
                                       float* out, long out_batch_stride, int* nonfinite, lidbox_stream_t stream);
 
+/* Ragged batches: B utterances of different lengths in ONE sample buffer and one launch.  Utterance b is
+ * signals[starts[b] .. starts[b] + n_b), has T_b = lidbox_num_frames(n_b, frame_length, frame_step) frames, and its features are rows
+ * frame_offsets[b] .. frame_offsets[b + 1] of out [total_frames, channels(kind)].  Those rows are bit-identical to what
+ * lidbox_extract_features_fwd_ex writes for that utterance alone (the reference's batch_size: 1), whatever else is in the batch,
+ * where that call takes the streaming kernel: a lone utterance of n_b samples has sig_stride = n_b, and with n_b % 4 != 0 the dense
+ * call reads it with scalar loads in the 4-wave kernel, whose results differ from the streaming kernel's in the last bit.
+ *   starts        [B]      device, samples; every start a multiple of 4 (the caller's duty: it is not read on the host)
+ *   tile_offsets  [B + 1]  device, prefix sum over ceil(T_b / 8): the kernel's unit of work is a tile of 8 frames, and a wave finds
+ *                          the utterance of its tile by a search in this array (utterances without frames are empty ranges).  An
+ *                          utterance WITH frames may be given an empty range too: the call then leaves its rows alone (the Python
+ *                          layer computes utterances whose length is no multiple of 4 through the dense call, see below)
+ *   frame_offsets [B + 1]  device, prefix sum over T_b
+ *   total_tiles = tile_offsets[B], total_frames = frame_offsets[B] (host copies; rows >= total_frames are never written;
+ *                          total_tiles == 0: LIDBOX_OK without a launch)
+ * The kernel only reads signals and the three arrays; samples behind an utterance's last frame (alignment gaps, the tail no frame
+ * owns) are never read into a result.  nonfinite as in lidbox_extract_features_fwd_ex.  workspace / workspace_bytes are reserved:
+ * the tile search needs no workspace, pass NULL / 0.
+ * lidbox_feat_plan_ragged_ok: 1 when the plan takes the ragged kernel for `kind` -- fft_length 512 with frame_length <= 512 (the
+ * fused path), mel bands that split into 64 runs (any plan for the spectrogram), tables that leave room for 8 waves, frame_length and
+ * frame_step multiples of 4.  Float32 sources only.
+ * LIDBOX_E_INVALID, with nothing written: a NULL pointer, a negative count, signals not 16-byte aligned, a plan that is not
+ * ragged_ok, total_tiles > total_frames, an utterance with (T_b + 8) * frame_step * 4 >= 2^31 (frame_offsets is copied back
+ * for this check only when (total_frames + 8) * frame_step * 4 >= 2^31).  B == 0 or total_frames == 0: LIDBOX_OK without a launch. */
+int lidbox_feat_plan_ragged_ok(const lidbox_feat_plan* plan, int kind);
+int lidbox_extract_features_ragged(const lidbox_feat_plan* plan, int kind, const float* signals, const long* starts,
+                                   const long* tile_offsets, const long* frame_offsets, int B, long total_tiles, long total_frames,
+                                   float* out, int* nonfinite, void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
+
 /* ------------------------------------------------------------------ normalisation (a7-a10) */
 
 /* lidbox/features/__init__.py:12-32  cmn / cmvn over the middle axis of x viewed as
@@ -131,6 +159,16 @@ int lidbox_cmvn_strided_fwd(const float* x, long outer, long R, long inner, long
  * (axis=1, T > window_len >= 2): REFLECT pad [w/2, w/2-1+(w&1)], per-window mean/std. */
 int lidbox_window_norm_fwd(const float* x, int B, int T, int C, int window_len,
                            int normalize_variance, float* out, lidbox_stream_t stream);
+
+/* cmn / cmvn and window_normalization for a ragged batch: x, out [total_rows, C]; utterance b owns rows row_offsets[b] ..
+ * row_offsets[b + 1] (device, [B + 1]) and is normalised over them bit-identically to lidbox_cmvn_fwd(outer = 1, R = T_b, inner = C)
+ * resp. to what features.window_normalization does with a [1, T_b, C] tensor: T_b <= window_len or window_len == -1 takes the CMVN
+ * branch, a longer utterance slides (window_len >= 2).  Utterances without rows are skipped.  x == out is allowed for
+ * lidbox_cmvn_ragged_fwd and for window_len == -1; the sliding branch reads rows it has passed and needs out != x. */
+int lidbox_cmvn_ragged_fwd(const float* x, const long* row_offsets, long B, int C, int normalize_variance, float* out,
+                           lidbox_stream_t stream);
+int lidbox_window_norm_ragged_fwd(const float* x, const long* row_offsets, long B, int C, int window_len, int normalize_variance,
+                                  float* out, lidbox_stream_t stream);
 
 /* min and max of n floats -> out2[0]=min, out2[1]=max (device).  First half of
  * features.feature_scaling (features/__init__.py:7-8, axis=None) and of audio.power_to_db's

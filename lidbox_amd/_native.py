@@ -86,6 +86,10 @@ _SIGS = {
     "lidbox_extract_features_fwd_shadow": (_i, [_vp, _i, _vp, _i, _i, _l, _vp, _l, _vp, _vp, _sz, _vp]),
     "lidbox_extract_features_fwd_ex": (_i, [_vp, _i, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "lidbox_extract_features_fwd_pcm16": (_i, [_vp, _i, _vp, _i, _i, _l, _vp, _l, _vp, _vp]),
+    "lidbox_feat_plan_ragged_ok": (_i, [_vp, _i]),
+    "lidbox_extract_features_ragged": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _l, _l, _vp, _vp, _vp, _sz, _vp]),
+    "lidbox_cmvn_ragged_fwd": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp]),
+    "lidbox_window_norm_ragged_fwd": (_i, [_vp, _vp, _l, _i, _i, _i, _vp, _vp]),
     "lidbox_cmvn_fwd": (_i, [_vp, _l, _l, _l, _i, _vp, _vp]),
     "lidbox_cmvn_strided_fwd": (_i, [_vp, _l, _l, _l, _l, _i, _vp, _l, _vp]),
     "lidbox_window_norm_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -990,9 +990,61 @@ template <bool SRC16> struct StreamRegs { typedef u32x4_s type; };
 template <> struct StreamRegs<true> { typedef u32x2_s type; };
 
 __device__ __forceinline__ unsigned wave_uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ long wave_uniform64(long v) {
+    return (long)(((unsigned long)wave_uniform((unsigned)((unsigned long)v >> 32)) << 32) | wave_uniform((unsigned)v));
+}
 
-template <int KIND, bool POW2, bool SHADOW, bool SRC16, int NL>
-__global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a) {
+// RAGGED form: B utterances of different lengths in one sample buffer, one dense [total_frames, C] output.  Utterance b starts at
+// signals + starts[b], has T_b = frame_offsets[b + 1] - frame_offsets[b] frames and owns tiles tile_offsets[b] .. tile_offsets[b + 1]
+// (a prefix sum over ceil(T_b / 8); an utterance given no tiles is left out) and output rows frame_offsets[b] ...  All three arrays
+// are only read.  B here is FusedArgs::B, ntiles = tile_offsets[B]; N, T, sig_stride, out_bs and tiles_per_utt are unused.
+constexpr int RAGGED_MAX_WAVES = 12;      // three per SIMD: 168 registers, which hold the tile search's state next to the tile's without scratch
+struct RaggedArgs : FusedArgs {
+    const long* starts;
+    const long* tile_offsets;
+    const long* frame_offsets;
+    long total_frames;
+};
+template <bool RAGGED> struct StreamArgs { typedef FusedArgs type; };
+template <> struct StreamArgs<true> { typedef RaggedArgs type; };
+
+// one tile of the ragged form, wave-uniform: its utterance, the utterance's tile range, frames and first output row, the tile's first frame
+struct RaggedTile {
+    unsigned b, ubeg, uend;
+    int T, t0;
+    long f0;
+};
+
+// The utterance that owns `tile` (< tile_offsets[B]): the LAST b with tile_offsets[b] <= tile, which skips the empty ranges of
+// utterances without frames wherever they lie.  `r` comes in as an earlier tile of this wave (a workgroup hands its tiles out in increasing
+// order, so the answer is not before it; uend == 0: none yet): inside the same utterance nothing is loaded, and that is the common
+// case -- a 2 s utterance has 25 tiles.  Otherwise a 64-ary search over the utterances behind it: every lane probes one offset and a
+// ballot counts the prefix that is <= tile, so 4096 utterances take two dependent loads where a binary search takes twelve.
+__device__ __forceinline__ RaggedTile ragged_tile(const RaggedArgs& a, const unsigned tile, RaggedTile r, const int ln) {
+    if (tile >= r.uend) {
+        unsigned lo = r.uend == 0 ? 0u : min(r.b + 1u, (unsigned)a.B - 1u);
+        unsigned n = (unsigned)a.B - lo;                     // candidates lo .. lo + n - 1, and tile_offsets[lo] <= tile
+        while (n > 1) {
+            const unsigned step = (n + 63u) >> 6;
+            const unsigned p = lo + ((unsigned)ln + 1u) * step;
+            const bool le = p < lo + n && a.tile_offsets[p] <= (long)tile;
+            const unsigned cnt = (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
+            lo += cnt * step;
+            n = min(step, n - cnt * step);
+        }
+        r.b = wave_uniform(lo);
+        r.ubeg = (unsigned)wave_uniform64(a.tile_offsets[r.b]);
+        r.uend = (unsigned)wave_uniform64(a.tile_offsets[r.b + 1]);
+        r.f0 = wave_uniform64(a.frame_offsets[r.b]);
+        r.T = (int)(wave_uniform64(a.frame_offsets[r.b + 1]) - r.f0);
+    }
+    r.t0 = (int)(tile - r.ubeg) * 8;
+    return r;
+}
+
+template <int KIND, bool POW2, bool SHADOW, bool SRC16, int NL, bool RAGGED = false>
+__global__ __launch_bounds__(RAGGED ? 64 * RAGGED_MAX_WAVES : 1024) void feat512_stream_kernel(const typename StreamArgs<RAGGED>::type a) {
+    static_assert(!RAGGED || (!SHADOW && !SRC16), "the ragged form reads float32 and writes no bf16 shadow");
     typedef typename StreamRegs<SRC16>::type xreg_t;
     constexpr int ESZ = SRC16 ? 2 : 4;                                  // bytes per source sample
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1021,20 +1073,33 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
     // 32 NL samples a lane group loads for the last frames reach past it into samples no frame owns, whose zero window weight would turn a
     // NaN / Inf there into a NaN frame (tf.signal.frame never reads them).  A float4 / short4 at a multiple of 4 samples is wholly inside
     // or wholly outside.
+    // (RAGGED: T is the utterance's own, see `nx` below)
     const unsigned utt_bytes = (unsigned)(((long)(a.T - 1) * a.S + a.L) * ESZ);
+
+    // RAGGED: the tile being computed and the wave's next one, each found once (ragged_tile) when the wave asks for it
+    RaggedTile cu = {0u, 0u, 0u, 0, 0, 0L}, nx = cu;
 
     // sample loads of local tile `local` (wave-uniform; past the workgroup's last tile: a descriptor of zero records, no traffic)
     xreg_t x[NL];                                          // NL = 13: frames of <= 416 samples, the window table is zero behind them
     auto issue = [&](unsigned local, const int ln) {
         const unsigned lane_off = (unsigned)((ln >> 3) * a.S + 4 * (ln & 7)) * ESZ;
         const bool on = local < ntl;
-        const unsigned tile = tile0 + (on ? local : 0u);
-        const unsigned b = tile / tpu;
-        const unsigned t0 = (tile - b * tpu) * 8u;
-        const char* base = reinterpret_cast<const char*>(a.signals) + (long)b * a.sig_stride * ESZ;
+        const char* base;
+        unsigned t0, nbytes;
+        if constexpr (RAGGED) {
+            base = reinterpret_cast<const char*>(a.signals + (on ? wave_uniform64(a.starts[nx.b]) : 0L));
+            t0 = (unsigned)nx.t0;
+            nbytes = (unsigned)(((long)(nx.T - 1) * a.S + a.L) * ESZ);
+        } else {
+            const unsigned tile = tile0 + (on ? local : 0u);
+            const unsigned b = tile / tpu;
+            t0 = (tile - b * tpu) * 8u;
+            base = reinterpret_cast<const char*>(a.signals) + (long)b * a.sig_stride * ESZ;
+            nbytes = utt_bytes;
+        }
         const unsigned lo = wave_uniform((unsigned)(uintptr_t)base), hi = wave_uniform((unsigned)((uintptr_t)base >> 32));
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-            reinterpret_cast<void*>(((uintptr_t)hi << 32) | lo), 0, on ? (int)utt_bytes : 0, 0x00020000);
+            reinterpret_cast<void*>(((uintptr_t)hi << 32) | lo), 0, on ? (int)nbytes : 0, 0x00020000);
         const int voff = (int)(t0 * (unsigned)a.S * ESZ + lane_off);
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
@@ -1055,6 +1120,8 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
         if (KIND == LIDBOX_FEAT_MFCC && tid < a.M * a.ncoef) t_dct = a.dct[tid];
     }
     unsigned cur = (unsigned)wave;
+    if constexpr (RAGGED)
+        if (cur < ntl) nx = ragged_tile(a, tile0 + cur, nx, lane0);
     issue(cur, lane0);
     if (tid < 512) s_win[tid] = t_win;
     if (tid < 256) {
@@ -1103,9 +1170,23 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
         if (lane == 0) nxt = (unsigned)__hip_atomic_fetch_add(s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         nxt = wave_uniform(nxt);
         asm volatile("" : "+s"(nxt));
-        const unsigned tile = tile0 + cur;
-        const unsigned b = tile / tpu;
-        const int t0 = (int)((tile - b * tpu) * 8u);
+        unsigned b;
+        int t0;
+        if constexpr (RAGGED) {
+            cu = nx;
+            if (nxt < ntl) nx = ragged_tile(a, tile0 + nxt, cu, lane);
+            b = cu.b;
+            t0 = cu.t0;
+        } else {
+            const unsigned tile = tile0 + cur;
+            b = tile / tpu;
+            t0 = (int)((tile - b * tpu) * 8u);
+        }
+        // first output element of the tile (C: floats per frame)
+        auto tile_out = [&](const int C) -> float* {
+            if constexpr (RAGGED) return a.out + (cu.f0 + t0) * C;
+            else return a.out + (long)b * a.out_bs + (long)t0 * C;
+        };
 
         // ---- 1. window.  lane q holds n2 = 2q (za) and 2q+1 (zb), n1 = 0..15: packed sample n = 16 n1 + n2 <-> reals 32 n1 + 4q .. + 3
         float2 za[16], zb[16];
@@ -1127,9 +1208,11 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
         // ---- 1'. the next tile's samples, into registers that are dead from here to the top of the loop
         issue(nxt, lane);
 
-        const int nvalid = min(8, a.T - t0);
+        int nvalid;                                       // frames of this tile inside the utterance (RAGGED: and inside the output)
+        if constexpr (RAGGED) nvalid = (int)min(8L, min((long)(cu.T - t0), a.total_frames - (cu.f0 + t0)));
+        else nvalid = min(8, a.T - t0);
         if (KIND == LIDBOX_FEAT_SPECTROGRAM) {
-            float* dst = a.out + (long)b * a.out_bs + (long)t0 * 257;
+            float* dst = tile_out(257);
             for (int ff = 0; ff < nvalid; ++ff) {
 #pragma unroll
                 for (int k0 = 0; k0 < 320; k0 += 64) {
@@ -1150,7 +1233,7 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
                 for (int u = 0; u < 8; ++u) wd[u] = 0.f;
                 segdct_tile<false, 2>(lane, a.dct_runs, a.dct_len, a.ncoef, a.M, wd, s_dct, s_stage, s_coef);      // two bands per batch: the next tile's samples are in flight
                 wave_lds_sync();
-                float* dst = a.out + (long)b * a.out_bs + (long)t0 * a.ncoef;
+                float* dst = tile_out(a.ncoef);
                 const int total = nvalid * a.ncoef;
                 for (int i = lane; i < total; i += 64) {
                     const float v = s_coef[i];
@@ -1158,7 +1241,7 @@ __global__ __launch_bounds__(1024) void feat512_stream_kernel(const FusedArgs a)
                     bad = fmaf(v, 0.f, bad);
                 }
             } else {
-                float* dst = a.out + (long)b * a.out_bs + (long)t0 * a.M;
+                float* dst = tile_out(a.M);
                 bad = store_mel_tile<SHADOW>(lane, nvalid * a.M, dst, SHADOW ? a.out16 + (dst - a.out) : nullptr, s_stage, bad);
             }
         }
@@ -1470,7 +1553,105 @@ int launch_stream(const lidbox_feat_plan* p, const FusedArgs& a, bool src16, int
     return src16 ? launch_stream_one<KIND, true, false, true>(a, nw, lds, st) : launch_stream_one<KIND, true, false, false>(a, nw, lds, st);
 }
 
+// the ragged form: float32 source, no shadow; power == 2 with pruned loads (NL = 13) where the frame allows, another power with NL = 16
+template <int KIND, bool POW2, int NL>
+int launch_ragged_nl(const RaggedArgs& a, int nw, size_t lds, hipStream_t st) {
+    static std::atomic<unsigned long long> attr_devs{0};
+    int dev = 0;
+    LBX_HIP(hipGetDevice(&dev));
+    if (dev >= 64 || !(attr_devs.load() >> dev & 1ull)) {
+        LBX_HIP(hipFuncSetAttribute((const void*)feat512_stream_kernel<KIND, POW2, false, false, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (dev < 64) attr_devs.fetch_or(1ull << dev);
+    }
+    hipLaunchKernelGGL((feat512_stream_kernel<KIND, POW2, false, false, NL, true>), dim3(a.nwg), dim3(64 * nw), lds, st, a);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+template <int KIND>
+int launch_ragged(const lidbox_feat_plan* p, const RaggedArgs& a, int nw, size_t lds, hipStream_t st) {
+    if (p->power != 2.0f) return launch_ragged_nl<KIND, false, 16>(a, nw, lds, st);
+    if (a.L <= 416) return launch_ragged_nl<KIND, true, 13>(a, nw, lds, st);
+    return launch_ragged_nl<KIND, true, 16>(a, nw, lds, st);
+}
+
+// bytes of the streaming kernel's tables in LDS for this plan and kind (mirrors the carve in the kernel)
+int stream_table_bytes(const lidbox_feat_plan* p, int kind) {
+    const int table_floats = 1536 + (kind == LIDBOX_FEAT_SPECTROGRAM ? 0 : mel_table_floats(true, p->M, p->nnz, p->seg_len)) +
+                             (kind == LIDBOX_FEAT_MFCC ? p->M * p->ncoef : 0);
+    return (table_floats * 4 + 4 + 15) & ~15;
+}
+
 }  // namespace
+
+extern "C" int lidbox_feat_plan_ragged_ok(const lidbox_feat_plan* p, int kind) {
+    if (!p || kind < LIDBOX_FEAT_SPECTROGRAM || kind > LIDBOX_FEAT_MFCC || !p->fused_ok) return 0;
+    if (kind == LIDBOX_FEAT_MFCC && p->ncoef <= 0) return 0;
+    if (!p->seg_ok && kind != LIDBOX_FEAT_SPECTROGRAM) return 0;
+    if (p->L % 4 != 0 || p->S % 4 != 0) return 0;
+    return (160 * 1024 - stream_table_bytes(p, kind)) / WAVE_SCRATCH >= 8 ? 1 : 0;
+}
+
+extern "C" int lidbox_extract_features_ragged(const lidbox_feat_plan* p, int kind, const float* signals, const long* starts,
+                                              const long* tile_offsets, const long* frame_offsets, int B, long total_tiles,
+                                              long total_frames, float* out, int* nonfinite, void* workspace, size_t workspace_bytes,
+                                              lidbox_stream_t stream) {
+    (void)workspace; (void)workspace_bytes;                      // the tile search needs none (see lidbox_hip.h)
+    LBX_ARG(p && signals && starts && tile_offsets && frame_offsets && out, "plan, signals, starts, tile_offsets, frame_offsets, out != NULL");
+    LBX_ARG(kind >= LIDBOX_FEAT_SPECTROGRAM && kind <= LIDBOX_FEAT_MFCC, "kind");
+    LBX_ARG(B >= 0 && total_tiles >= 0 && total_frames >= 0, "B >= 0, total_tiles >= 0, total_frames >= 0");
+    LBX_ARG((((uintptr_t)signals) & 15) == 0, "signals must be 16-byte aligned (and every start a multiple of 4 samples)");
+    LBX_ARG(lidbox_feat_plan_ragged_ok(p, kind),
+            "the plan does not take the ragged kernel (fft_length 512, frame_length and frame_step multiples of 4, mel bands that split "
+            "into 64 runs): group the utterances by length and call lidbox_extract_features_fwd_ex");
+    LBX_ARG(total_tiles < (1L << 31) && total_tiles <= total_frames, "total_tiles < 2^31 and total_tiles <= total_frames");
+    if (B == 0 || total_frames == 0 || total_tiles == 0) return LIDBOX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // an utterance's byte offsets are 32-bit in the kernel: (T_b + 8) * S * 4 < 2^31 as in the dense call.  T_b <= total_frames, so
+    // the offsets are only read back (one synchronous copy) when the total does not already show it.
+    if ((total_frames + 8) * p->S * 4 >= (1L << 31)) {
+        std::vector<long> fo((size_t)B + 1);
+        LBX_HIP(hipMemcpyAsync(fo.data(), frame_offsets, fo.size() * sizeof(long), hipMemcpyDeviceToHost, st));
+        LBX_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b)
+            LBX_ARG((fo[b + 1] - fo[b] + 8) * p->S * 4 < (1L << 31), "an utterance has too many frames: (T_b + 8) * frame_step * 4 must stay below 2^31");
+    }
+    RaggedArgs a;
+    a.signals = signals; a.sig_stride = 0; a.B = B; a.N = 0; a.T = 0;
+    a.L = p->L; a.S = p->S; a.power_half = 0.5f * p->power;
+    a.M = p->M; a.ncoef = p->ncoef; a.nnz = p->nnz;
+    a.seg_len = p->seg_len; a.seg_steps = p->seg_steps; a.seg_meta = p->d_seg_meta; a.seg_w = p->d_seg_w;
+    a.dct_runs = p->ncoef > 0 ? (64 / p->ncoef < 1 ? 1 : 64 / p->ncoef) : 1;                 // as lidbox_extract_features_fwd_ex
+    if (a.dct_runs > p->M) a.dct_runs = p->M;
+    a.dct_len = (p->M + a.dct_runs - 1) / a.dct_runs;
+    a.dct_runs = (p->M + a.dct_len - 1) / a.dct_len;
+    a.win512 = p->d_win512; a.tw256 = p->d_tw256; a.tw512 = p->d_tw512;
+    a.mel_start = p->d_mel_start; a.mel_cnt = p->d_mel_cnt; a.mel_off = p->d_mel_off;
+    a.mel_w = p->d_mel_w; a.dct = p->d_dct; a.out = out; a.out_bs = 0;
+    a.out16 = nullptr;
+    a.nonfinite = nonfinite;
+    a.tiles_per_utt = 0;
+    a.ntiles = total_tiles;
+    a.iters = 0;
+    a.starts = starts; a.tile_offsets = tile_offsets; a.frame_offsets = frame_offsets; a.total_frames = total_frames;
+    // the work split of the dense launch: every CU the same number of consecutive tiles, waves capped at that number
+    const int table_bytes = stream_table_bytes(p, kind);
+    int nw = (160 * 1024 - table_bytes) / WAVE_SCRATCH;
+    if (nw > RAGGED_MAX_WAVES) nw = RAGGED_MAX_WAVES;
+    int ncu = 256;
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device);
+    if (ncu < 1) ncu = 256;
+    a.tiles_per_wg = (int)lbx_cdiv(a.ntiles, (long)ncu);
+    a.nwg = (unsigned)lbx_cdiv(a.ntiles, (long)a.tiles_per_wg);
+    if (a.tiles_per_wg < nw) nw = a.tiles_per_wg;
+    const size_t lds = (size_t)table_bytes + (size_t)nw * WAVE_SCRATCH;
+    switch (kind) {
+        case LIDBOX_FEAT_SPECTROGRAM: return launch_ragged<LIDBOX_FEAT_SPECTROGRAM>(p, a, nw, lds, st);
+        case LIDBOX_FEAT_MEL: return launch_ragged<LIDBOX_FEAT_MEL>(p, a, nw, lds, st);
+        case LIDBOX_FEAT_LOGMEL: return launch_ragged<LIDBOX_FEAT_LOGMEL>(p, a, nw, lds, st);
+        default: return launch_ragged<LIDBOX_FEAT_MFCC>(p, a, nw, lds, st);
+    }
+}
 
 extern "C" int lidbox_feat_plan_is_fused(const lidbox_feat_plan* p, int kind, const float* signals,
                                          long sig_stride) {

@@ -14,57 +14,72 @@
 
 namespace {
 
-// x viewed as [outer, R, inner]; one workgroup per (outer, column tile of cw columns);
-// 256 threads = cw columns x (256/cw) row groups.
-// x and out may be the same buffer (every element is read and written by the same thread, the write comes last);
-// xs / os: floats between consecutive `outer` slices (>= R * inner).
-__global__ __launch_bounds__(256) void cmvn_kernel(const float* x, long outer, long R, long inner, long xs, long os,
-                                                   int cw, int normalize_variance,
-                                                   float* out) {
-    __shared__ float red[256];
+// One [R, inner] slice for the cw columns of this workgroup: 256 threads = cw columns x (256 / cw) row groups; mean, then the
+// centred variance, then the write.  xp / op point at the thread's column; they may alias (every element is read and written by
+// the same thread, the write comes last).  Block-uniform: every thread of the workgroup calls it.
+__device__ __forceinline__ void cmvn_slice(const float* xp, float* op, const long R, const long inner, const int cw, const bool active,
+                                           const int normalize_variance, float* red) {
     const int tid = threadIdx.x;
     const int col = tid % cw, g = tid / cw, ng = 256 / cw;
-    const long c = (long)blockIdx.x * cw + col;
-    const bool active = c < inner;
-    // grid.y is capped at 65 535: a workgroup walks the outer slices o = blockIdx.y, + gridDim.y, ... (block-uniform trip count)
-    for (long o = blockIdx.y; o < outer; o += gridDim.y) {
-        const float* xp = x + o * xs + c;
-        float* op = out + o * os + c;
+    float s = 0.f;
+    if (active)
+        for (long r = g; r < R; r += ng) s += xp[r * inner];
+    __syncthreads();                                 // the previous slice's readers of red[] are done
+    red[tid] = s;
+    __syncthreads();
+    for (int h = ng / 2; h > 0; h >>= 1) {
+        if (g < h) red[tid] += red[tid + h * cw];
+        __syncthreads();
+    }
+    const float mean = red[col] / (float)R;
+    __syncthreads();
 
-        float s = 0.f;
+    float sd = 1.f;
+    if (normalize_variance) {
+        float v = 0.f;
         if (active)
-            for (long r = g; r < R; r += ng) s += xp[r * inner];
-        __syncthreads();                                 // the previous slice's readers of red[] are done
-        red[tid] = s;
+            for (long r = g; r < R; r += ng) {
+                const float d = xp[r * inner] - mean;
+                v = fmaf(d, d, v);
+            }
+        red[tid] = v;
         __syncthreads();
         for (int h = ng / 2; h > 0; h >>= 1) {
             if (g < h) red[tid] += red[tid + h * cw];
             __syncthreads();
         }
-        const float mean = red[col] / (float)R;
-        __syncthreads();
-
-        float sd = 1.f;
-        if (normalize_variance) {
-            float v = 0.f;
-            if (active)
-                for (long r = g; r < R; r += ng) {
-                    const float d = xp[r * inner] - mean;
-                    v = fmaf(d, d, v);
-                }
-            red[tid] = v;
-            __syncthreads();
-            for (int h = ng / 2; h > 0; h >>= 1) {
-                if (g < h) red[tid] += red[tid + h * cw];
-                __syncthreads();
-            }
-            sd = sqrtf(red[col] / (float)R);             // population std of x
+        sd = sqrtf(red[col] / (float)R);             // population std of x
+    }
+    if (active)
+        for (long r = g; r < R; r += ng) {
+            const float d = xp[r * inner] - mean;
+            op[r * inner] = normalize_variance ? (sd != 0.f ? d / sd : 0.f) : d;   // divide_no_nan
         }
-        if (active)
-            for (long r = g; r < R; r += ng) {
-                const float d = xp[r * inner] - mean;
-                op[r * inner] = normalize_variance ? (sd != 0.f ? d / sd : 0.f) : d;   // divide_no_nan
-            }
+}
+
+// x viewed as [outer, R, inner]; one workgroup per (outer, column tile of cw columns).
+// x and out may be the same buffer; xs / os: floats between consecutive `outer` slices (>= R * inner).
+__global__ __launch_bounds__(256) void cmvn_kernel(const float* x, long outer, long R, long inner, long xs, long os,
+                                                   int cw, int normalize_variance,
+                                                   float* out) {
+    __shared__ float red[256];
+    const long c = (long)blockIdx.x * cw + threadIdx.x % cw;
+    // grid.y is capped at 65 535: a workgroup walks the outer slices o = blockIdx.y, + gridDim.y, ... (block-uniform trip count)
+    for (long o = blockIdx.y; o < outer; o += gridDim.y)
+        cmvn_slice(x + o * xs + c, out + o * os + c, R, inner, cw, c < inner, normalize_variance, red);
+}
+
+// The ragged form: x is [total_rows, C], utterance b owns rows row_offsets[b] .. row_offsets[b + 1] and is normalised over them exactly
+// as cmvn_kernel normalises a [1, T_b, C] tensor (same cw, same row groups, same order).  Utterances without rows are skipped, and so
+// are those with more than max_rows rows when max_rows >= 0 (the sliding branch of the window form takes them).
+__global__ __launch_bounds__(256) void cmvn_ragged_kernel(const float* x, const long* __restrict__ row_offsets, long B, long C, long max_rows,
+                                                          int cw, int normalize_variance, float* out) {
+    __shared__ float red[256];
+    const long c = (long)blockIdx.x * cw + threadIdx.x % cw;
+    for (long b = blockIdx.y; b < B; b += gridDim.y) {
+        const long r0 = row_offsets[b], R = row_offsets[b + 1] - r0;
+        if (R <= 0 || (max_rows >= 0 && R > max_rows)) continue;          // block-uniform
+        cmvn_slice(x + r0 * C + c, out + r0 * C + c, R, C, cw, c < C, normalize_variance, red);
     }
 }
 
@@ -82,14 +97,8 @@ __device__ __forceinline__ int reflect_idx(int i, int T) {
 // float64 on float32 data shifted by the channel's first sample agrees with tf.math.reduce_std's two-pass result
 // to float32 rounding (the tests compare with the float64 two-pass oracle at 1e-3 like every other row).
 // Consecutive threads are consecutive channels: every access is a coalesced row segment.
-__global__ __launch_bounds__(256) void window_norm_kernel(const float* __restrict__ x, int B, int T, int C, int w,
-                                                          int normalize_variance, float* __restrict__ out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * C) return;
-    const int c = (int)(i % C);
-    const long b = i / C;
-    const float* xb = x + b * (long)T * C + c;
-    float* ob = out + b * (long)T * C + c;
+__device__ __forceinline__ void window_norm_channel(const float* __restrict__ xb, float* __restrict__ ob, const int T, const int C, const int w,
+                                                    const int normalize_variance) {
     const int left = w / 2;
     const float x0 = xb[0];
     double s = 0.0, q = 0.0;
@@ -127,6 +136,29 @@ __global__ __launch_bounds__(256) void window_norm_kernel(const float* __restric
             q += e * e - a * a;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void window_norm_kernel(const float* __restrict__ x, int B, int T, int C, int w,
+                                                          int normalize_variance, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * C) return;
+    const int c = (int)(i % C);
+    const long b = i / C;
+    window_norm_channel(x + b * (long)T * C + c, out + b * (long)T * C + c, T, C, w, normalize_variance);
+}
+
+// The ragged form of the sliding branch: utterance b = rows row_offsets[b] .. row_offsets[b + 1] of [total_rows, C]; only utterances
+// with more than w rows slide (cmvn_ragged_kernel with max_rows = w normalises the others, as window_normalization decides for a
+// [1, T_b, C] tensor).
+__global__ __launch_bounds__(256) void window_norm_ragged_kernel(const float* __restrict__ x, const long* __restrict__ row_offsets, long B, int C,
+                                                                 int w, int normalize_variance, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * C) return;
+    const int c = (int)(i % C);
+    const long b = i / C;
+    const long r0 = row_offsets[b], T = row_offsets[b + 1] - r0;
+    if (T <= w) return;
+    window_norm_channel(x + r0 * C + c, out + r0 * C + c, (int)T, C, w, normalize_variance);
 }
 
 constexpr int MM_MAX_WG = 1024;
@@ -288,6 +320,40 @@ extern "C" int lidbox_window_norm_fwd(const float* x, int B, int T, int C, int w
     if (total == 0) return LIDBOX_OK;
     hipLaunchKernelGGL(window_norm_kernel, dim3((unsigned)lbx_cdiv((long)B * C, 256)), dim3(256), 0,
                        (hipStream_t)stream, x, B, T, C, window_len, normalize_variance, out);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+namespace {
+int cmvn_ragged_launch(const float* x, const long* row_offsets, long B, int C, long max_rows, int normalize_variance, float* out, hipStream_t st) {
+    int cw = 64;                                             // the rule of lidbox_cmvn_strided_fwd for inner = C
+    while (cw > 1 && cw / 2 >= C) cw /= 2;
+    dim3 grid((unsigned)lbx_cdiv((long)C, (long)cw), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL(cmvn_ragged_kernel, grid, dim3(256), 0, st, x, row_offsets, B, (long)C, max_rows, cw, normalize_variance, out);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+}  // namespace
+
+extern "C" int lidbox_cmvn_ragged_fwd(const float* x, const long* row_offsets, long B, int C, int normalize_variance, float* out,
+                                      lidbox_stream_t stream) {
+    LBX_ARG(x && row_offsets && out, "x, row_offsets, out != NULL");
+    LBX_ARG(B >= 0 && C >= 0, "B >= 0, C >= 0");
+    if (B == 0 || C == 0) return LIDBOX_OK;
+    return cmvn_ragged_launch(x, row_offsets, B, C, -1, normalize_variance, out, (hipStream_t)stream);
+}
+
+extern "C" int lidbox_window_norm_ragged_fwd(const float* x, const long* row_offsets, long B, int C, int window_len, int normalize_variance,
+                                             float* out, lidbox_stream_t stream) {
+    LBX_ARG(x && row_offsets && out, "x, row_offsets, out != NULL");
+    LBX_ARG(B >= 0 && C >= 0, "B >= 0, C >= 0");
+    LBX_ARG(window_len == -1 || window_len >= 2, "window_len is -1 (whole utterance) or >= 2");
+    LBX_ARG(window_len == -1 || x != out, "the sliding branch reads rows it has already passed: x and out must differ unless window_len is -1");
+    if (B == 0 || C == 0) return LIDBOX_OK;
+    const int rc = cmvn_ragged_launch(x, row_offsets, B, C, window_len, normalize_variance, out, (hipStream_t)stream);
+    if (rc != LIDBOX_OK || window_len == -1) return rc;
+    hipLaunchKernelGGL(window_norm_ragged_kernel, dim3((unsigned)lbx_cdiv(B * C, 256L)), dim3(256), 0, (hipStream_t)stream, x, row_offsets, B, C,
+                       window_len, normalize_variance, out);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

@@ -30,7 +30,12 @@ schema (`_feature_extraction_kwargs_to_args`, steps.py:94-104):
     {"type": "logmelspectrogram" | "mfcc" | "melspectrogram" | "spectrogram" | "db_spectrogram",
      "spectrogram": {...}, "melspectrogram": {...}, "mfcc": {...}, "db_spectrogram": {...},
      "sample_minmax_scaling": {...}, "window_normalization": {...},
-     "batch_size": 1 | "group_by_input_length": {"max_batch_size": n}, "device": ...}
+     "batch_size": 1 | "group_by_input_length": {"max_batch_size": n} | "ragged_batch_size": n, "device": ...}
+
+`ragged_batch_size: n` (lidbox_amd only, like `launch_batch` of the signal steps) puts n consecutive elements of ANY lengths into
+one launch of the ragged feature kernel; every element gets what `batch_size: 1` gives it, bit for bit, and the element order is
+kept.  That is the pipeline without signal chunking: VAD leaves every utterance its own length, so `group_by_input_length` finds
+groups of one.  `normalize` has the matching opt-in `ragged: true`.
 
 The reference maps this over a tf.data.Dataset (batch -> map -> unbatch); here `ds` is any
 iterable of element dicts holding at least `signal` (1-D float32 tensor or array) and
@@ -114,6 +119,9 @@ def extract_features(ds, config):
     device = _get_device_or_default(config)
     logger.info("Extracting '%s' features on device '%s' with arguments:\n  %s", feature_type, device,
                 "\n  ".join(repr(a) for a in args[1:]))
+    if "ragged_batch_size" in config:
+        yield from _extract_features_ragged(ds, config, feature_type, args, device)
+        return
     for batch in _batches(ds, config):
         sigs = [torch.as_tensor(x["signal"]) for x in batch]
         if not all(t.dtype == torch.int16 for t in sigs):                            # 16-bit PCM stays int16: the kernel reads it in place
@@ -122,6 +130,23 @@ def extract_features(ds, config):
         rates = [int(x["sample_rate"]) for x in batch]
         feats = tf_utils.extract_features(signals, rates, *args)
         for x, f in zip(batch, feats.unbind(0)):                                     # unbatch (:736): one call for all the views
+            yield dict(x, input=f, feature_type=feature_type)
+
+
+def _extract_features_ragged(ds, config, feature_type, args, device):
+    """`ragged_batch_size: n`: n elements of any lengths per feature launch (tf_utils.extract_features_ragged), in input order"""
+    if "group_by_input_length" in config:
+        raise ValueError("ragged_batch_size and group_by_input_length exclude each other: a ragged batch needs no equal lengths")
+    n = int(config["ragged_batch_size"])
+    if n < 1:
+        raise ValueError("ragged_batch_size must be at least 1")
+    for batch in _launch_batches(ds, n):
+        sigs = [torch.as_tensor(x["signal"]) for x in batch]
+        # 16-bit PCM: scaled as the dense call reads it in place (value / 32768)
+        sigs = [audio_features.pcm16_to_float(t, 1, device=device) if t.dtype == torch.int16 else t for t in sigs]
+        rates = [int(x["sample_rate"]) for x in batch]
+        feats = tf_utils.extract_features_ragged(signal_ops.RaggedSignals.from_list(sigs, device=device), rates, *args)
+        for x, f in zip(batch, feats):
             yield dict(x, input=f, feature_type=feature_type)
 
 
@@ -484,12 +509,25 @@ def create_input_chunks(ds, length, step, launch_batch=256):
 
 def normalize(ds, config):
     """reference steps.py:821-834: batches of config.get("batch_size", 1) elements, features.cmvn(x[key], **kwargs) on the
-    stacked batch, unbatched.  Elements of one batch must share the shape (tf.data's `batch` has the same requirement)."""
+    stacked batch, unbatched.  Elements of one batch must share the shape (tf.data's `batch` has the same requirement).
+    `ragged: true` (lidbox_amd only): the [T, C] values of a batch may differ in T; one launch of features.cmvn_ragged gives every
+    element what `batch_size: 1` gives it, bit for bit.  Axis 1 (time) only."""
     logger.info("Applying normalization with config:\n  %s", _dict_to_logstring(config))
     key = config["key"]
     kwargs = config.get("kwargs", {})
+    ragged = bool(config.get("ragged", False))
+    if ragged and set(kwargs) - {"axis"} or ragged and kwargs.get("axis", 1) != 1:
+        raise ValueError("ragged normalization takes axis=1 (time) only, got kwargs %r" % (kwargs,))
     for batch in _launch_batches(ds, int(config.get("batch_size", 1))):
         values = [torch.as_tensor(x[key]) for x in batch]
+        if ragged:
+            if any(v.dim() != 2 or v.shape[1] != values[0].shape[1] for v in values):
+                raise ValueError("ragged normalization needs [T, C] '%s' tensors with one C" % key)
+            offsets = np.concatenate(([0], np.cumsum([int(v.shape[0]) for v in values])))
+            normalized = features.cmvn_ragged(torch.cat(values), offsets)
+            for x, lo, hi in zip(batch, offsets[:-1], offsets[1:]):
+                yield dict(x, **{key: normalized[int(lo):int(hi)]})
+            continue
         if any(v.shape != values[0].shape for v in values):
             raise ValueError("cannot batch '%s' tensors of different shapes for normalization" % key)
         normalized = features.cmvn(torch.stack(values), **kwargs)

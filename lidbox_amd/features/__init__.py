@@ -3,6 +3,7 @@ Counterpart of lidbox/features/__init__.py: feature_scaling, cmn, cmvn, window_n
 with the reference's signatures (file:line cited per function), over torch tensors on the HIP
 device.  Arithmetic runs in liblidbox_hip.so; there is no CPU fallback.
 """
+import numpy as np
 import torch
 
 from .. import _native as nv
@@ -84,6 +85,57 @@ def cmn(X, axis=1):
 def cmvn(X, axis=1):
     """reference lidbox/features/__init__.py:22-32 (population std, divide_no_nan)."""
     return _cmvn(X, axis, True)
+
+
+def _ragged_rows(X, row_offsets, out):
+    X = nv.require_gpu_tensor(X, "X", torch.float32)
+    if X.dim() != 2 or not X.is_contiguous():
+        raise ValueError("X must be a contiguous [total_rows, C] tensor")
+    ro = np.ascontiguousarray(np.asarray(row_offsets, np.int64).reshape(-1))
+    if len(ro) < 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or int(ro[-1]) != X.shape[0]:
+        raise ValueError("row_offsets must rise from 0 to the %d rows of X" % X.shape[0])
+    if out is None:
+        out = torch.empty_like(X)
+    elif out is not X:
+        nv.require_gpu_tensor(out, "out", torch.float32)
+        if out.shape != X.shape or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of X's shape")
+    return X, ro, out
+
+
+def _cmvn_ragged(X, row_offsets, normalize_variance, out):
+    X, ro, out = _ragged_rows(X, row_offsets, out)
+    if X.numel():
+        ro_d = torch.from_numpy(ro).to(X.device)
+        with torch.cuda.device(X.device):
+            nv.check(nv.lib.lidbox_cmvn_ragged_fwd(nv.ptr(X), nv.ptr(ro_d), len(ro) - 1, X.shape[1], int(bool(normalize_variance)),
+                                                   nv.ptr(out), nv.current_stream()))
+    return out
+
+
+def cmn_ragged(X, row_offsets, out=None):
+    """`cmn(axis=1)` for utterances of different lengths: X [total_rows, C], utterance b = rows row_offsets[b] .. row_offsets[b + 1]
+    (host array, B + 1 entries); each is normalised as `cmn` normalises it alone as [1, T_b, C], bit for bit.  out=X: in place."""
+    return _cmvn_ragged(X, row_offsets, False, out)
+
+
+def cmvn_ragged(X, row_offsets, out=None):
+    """`cmvn(axis=1)` for utterances of different lengths (see `cmn_ragged`)."""
+    return _cmvn_ragged(X, row_offsets, True, out)
+
+
+def window_normalization_ragged(X, row_offsets, axis=1, window_len=-1, normalize_variance=True):
+    """`window_normalization` for utterances of different lengths (layout as `cmn_ragged`): every utterance gets what the dense
+    function gives it alone as [1, T_b, C] -- T_b <= window_len or window_len == -1: cmvn / cmn, otherwise the sliding window."""
+    if axis != 1:
+        raise ValueError("ragged window normalization is defined on axis=1 (the time axis of every utterance)")
+    X, ro, out = _ragged_rows(X, row_offsets, None)
+    if X.numel():
+        ro_d = torch.from_numpy(ro).to(X.device)
+        with torch.cuda.device(X.device):
+            nv.check(nv.lib.lidbox_window_norm_ragged_fwd(nv.ptr(X), nv.ptr(ro_d), len(ro) - 1, X.shape[1], int(window_len),
+                                                          int(bool(normalize_variance)), nv.ptr(out), nv.current_stream()))
+    return out
 
 
 def window_normalization(X, axis=1, window_len=-1, normalize_variance=True):

@@ -88,6 +88,54 @@ class FeaturePlan:
                 call()
         return out
 
+    def ragged_ok(self, kind):
+        """True when this plan takes the ragged kernel for `kind` (lidbox_feat_plan_ragged_ok)"""
+        return bool(nv.lib.lidbox_feat_plan_ragged_ok(self.handle, kind))
+
+    def run_ragged(self, kind, r, out=None, nonfinite=None):
+        """r: a signal_ops.RaggedSignals of B utterances of any lengths -> (out [total_frames, C], frame_offsets_host [B + 1]):
+        rows frame_offsets[b] .. frame_offsets[b + 1] are utterance b's features, bit-identical to `run` on that utterance alone.
+        One launch of the ragged kernel where the plan and the buffer allow it (`ragged_ok`, a 16-byte aligned buffer, starts that are
+        multiples of 4 samples); otherwise the utterances are grouped by length and each group goes through `run`: the same layout
+        and the same values.  Utterances whose length is no multiple of 4 always go that way: alone, `run` reads them with scalar
+        loads in another kernel, whose last bits differ from the streaming kernels', and the contract is what `run` gives (after
+        VAD and chunking every length is a multiple of the VAD frame, so this is rare).  nonfinite as in `run`."""
+        if not isinstance(r, signal_ops.RaggedSignals):
+            raise TypeError("run_ragged takes a signal_ops.RaggedSignals")
+        flat, dev, S = r.flat, r.flat.device, self.frame_step
+        to_h, fo_h = signal_ops.ragged_frame_plan(r.lengths_host, self.frame_length, S)
+        total, C = int(fo_h[-1]), self.channels(kind)
+        if out is None:
+            out = torch.empty((total, C), dtype=torch.float32, device=dev)
+        else:
+            nv.require_gpu_tensor(out, "out", torch.float32)
+            if tuple(out.shape) != (total, C) or not out.is_contiguous():
+                raise ValueError("out must be a contiguous [%d, %d] tensor" % (total, C))
+        if r.B == 0 or total == 0:
+            return out, fo_h
+        if (int(np.diff(fo_h).max()) + 8) * S * 4 >= 2 ** 31:
+            raise ValueError("an utterance has too many frames for one call: (T + 8) * frame_step * 4 must stay below 2^31")
+        dense = np.diff(fo_h) > 0                                                 # utterances left to `run`
+        if self.ragged_ok(kind) and flat.data_ptr() % 16 == 0 and not (r.starts_host % signal_ops.ALIGN).any():
+            dense &= r.lengths_host % 4 != 0
+            to_h = np.concatenate(([0], np.cumsum(np.where(dense, 0, np.diff(to_h)))))      # no tiles for them: the kernel leaves their rows alone
+            flag_ptr = None
+            if nonfinite is not None:
+                flag_ptr = nonfinite.ptr if isinstance(nonfinite, FiniteFlag) else nv.ptr(nv.require_gpu_tensor(nonfinite, "nonfinite", torch.int32))
+            csr = torch.from_numpy(np.stack((to_h, fo_h))).to(dev)               # one copy for both arrays
+            with torch.cuda.device(dev):
+                nv.check(nv.lib.lidbox_extract_features_ragged(self.handle, kind, nv.ptr(flat), nv.ptr(r.starts), nv.ptr(csr[0]), nv.ptr(csr[1]),
+                                                               r.B, int(to_h[-1]), total, nv.ptr(out), flag_ptr, None, 0, nv.current_stream()))
+        groups = {}
+        for b in np.flatnonzero(dense):
+            groups.setdefault(int(r.lengths_host[b]), []).append(int(b))
+        sigs = r.split() if groups else None
+        for idx in groups.values():
+            feats = self.run(kind, torch.stack([sigs[b] for b in idx]), nonfinite=nonfinite)
+            for b, f in zip(idx, feats.unbind(0)):
+                out[int(fo_h[b]):int(fo_h[b + 1])].copy_(f)
+        return out, fo_h
+
     def _pcm_in_place(self, signals, stride):
         """what lidbox_extract_features_fwd_ex asks of a 16-bit source (include/lidbox_hip.h): the fused fft_length-512 kernel with
         power 2, 8-byte aligned rows, row stride / frame_length / frame_step multiples of 4"""

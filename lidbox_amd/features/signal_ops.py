@@ -84,6 +84,20 @@ class RaggedSignals:
         return [flat[int(s):int(s) + int(n)] for s, n in zip(self.starts_host, self.lengths_host)]
 
 
+def ragged_frame_plan(lengths, L, S):
+    """the two CSR arrays lidbox_extract_features_ragged reads, as host int64 arrays of len(lengths) + 1 entries:
+    (tile_offsets, frame_offsets) = prefix sums over ceil(T_b / 8) and over T_b, T_b = lidbox_num_frames(lengths[b], L, S)"""
+    L, S = int(L), int(S)
+    if L < 1 or S < 1:
+        raise ValueError("frame length and frame step must be at least one sample")
+    n = np.asarray(lengths, np.int64).reshape(-1)
+    if (n < 0).any():
+        raise ValueError("signal lengths must not be negative")
+    T = np.where(n >= L, 1 + (n - L) // S, 0)
+    zero = np.zeros(1, np.int64)
+    return np.concatenate((zero, np.cumsum((T + 7) // 8))).astype(np.int64), np.concatenate((zero, np.cumsum(T))).astype(np.int64)
+
+
 def frame_rms(r, frame_len):
     """RMS of every non-overlapping frame (audio.py:314-317) -> (rms [total_frames], frame CSR host / device)"""
     frame_len = int(frame_len)
