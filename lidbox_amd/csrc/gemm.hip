@@ -1326,7 +1326,8 @@ extern "C" int lidbox_gemm_nt_carry(lidbox_rows_t A, const float* Bm, long ldb, 
     const int m = jobs_in(jobs, njobs, js);
     LBX_ARG(m >= 0, "at most 2 non-empty jobs per call");
     for (int i = 0; i < m; ++i) LBX_ARG(js[i].splits >= 0, "an optimizer-prepare job runs through lidbox_reduce_jobs_run only");
-    for (int i = 0; i < m; ++i) LBX_ARG((const void*)js[i].P != workspace, "a job's slices live in this call's workspace");
+    // (a zero job has no slices: P == NULL must not be mistaken for a call without a workspace)
+    for (int i = 0; i < m; ++i) LBX_ARG(!js[i].P || (const void*)js[i].P != workspace, "a job's slices live in this call's workspace");
     Carry carry;
     carry.jobs = js;
     carry.njobs = (m > 0 && getenv("LIDBOX_GEMM_NO_CARRY") == nullptr) ? m : 0;
@@ -1384,7 +1385,8 @@ extern "C" int lidbox_gemm_nt_tn_carry(lidbox_rows_t dY, const float* W, long ld
     const int npend = jobs_in(jobs, njobs, pend);
     LBX_ARG(npend >= 0 && npend < MAX_CARRY, "at most 1 non-empty pending job per call");
     for (int i = 0; i < npend; ++i)
-        LBX_ARG((const void*)pend[i].P != ws_nt && (const void*)pend[i].P != ws_tn, "a pending job's slices live in this call's workspaces");
+        LBX_ARG(!pend[i].P || ((const void*)pend[i].P != ws_nt && (const void*)pend[i].P != ws_tn),
+                "a pending job's slices live in this call's workspaces");
     for (int i = 0; i < npend; ++i) LBX_ARG(pend[i].splits >= 0, "an optimizer-prepare job runs through lidbox_reduce_jobs_run only");
     const long M = (long)dY.batch * dY.rows_per_batch;
     bool pair = dma_mode() != 0 && getenv("LIDBOX_GEMM_NO_PAIR") == nullptr && M >= 1 && N >= 1 && K1 >= 1 && Co >= 1 && W && dW && ws_tn &&
