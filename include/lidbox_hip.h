@@ -590,6 +590,31 @@ int lidbox_avg_pool_fwd(const float* x, int B, int T, int C, long batch_stride, 
 int lidbox_avg_pool_bwd(const float* x, const float* dout, int B, int T, int C, long batch_stride,
                         long row_stride, int relu_mask, float* dx, lidbox_stream_t stream);
 
+/* ------------------------------------------------------------------ ragged model pass (csrc/ragged.hip)
+ *
+ * Utterances of different lengths share ONE row buffer per level of a causal Conv1D stack (lidbox_amd/models/ragged.py has the
+ * layout): utterance b owns the segment of rows seg_offsets[b] .. seg_offsets[b + 1], which starts with `pad` zero rows (the causal
+ * padding of the layer that reads the level), then holds its frames, then slack.  A `batch = 1` lidbox_rows_t over such a buffer
+ * makes every Conv1D one lidbox_gemm_nn call.  All offsets and lengths are int64 device arrays; B is not capped at 65 535; rows are
+ * C floats apart unless a row stride is given; 16-byte accesses when C % 4 == 0 and the pointers are 16-byte aligned, scalar ones
+ * otherwise.  B == 0 returns LIDBOX_OK and touches nothing. */
+
+/* src [total_T, C], utterance b = rows src_offsets[b] .. src_offsets[b + 1] (device, [B + 1]) -> dst, the level-0 buffer: EVERY row
+ * of every segment is written (pad zero rows, the frames, zeros up to the next segment -- frames that do not fit behind the pad are
+ * dropped, never written elsewhere), and `tail_rows` zero rows behind the last segment, so a reused buffer shows no stale rows. */
+int lidbox_ragged_pack_rows(const float* src, const long* src_offsets, float* dst, const long* seg_offsets, long B, int C, int pad,
+                            long tail_rows, lidbox_stream_t stream);
+/* zeroes the first `pad` rows of every segment (at most the segment): the repair behind a GEMM that wrote all rows of a level */
+int lidbox_ragged_zero_rows(float* x, const long* seg_offsets, long B, int C, int pad, lidbox_stream_t stream);
+/* GlobalMeanStddevPooling1D / GlobalAveragePooling1D per utterance: the lengths[b] >= 1 rows (row_stride floats apart) from row
+ * seg_offsets[b] of x -> out [B, 2C] = (mean, sqrt(clip(var, 1e-10, FLT_MAX))) resp. [B, C].  Every utterance, whatever its
+ * length, gets the arithmetic of lidbox_stats_pool_fwd's long-utterance kernel: two passes, 16 time groups summed in order and
+ * combined through LDS in a fixed order -- so a result does not depend on the utterance's neighbours or its place in the batch. */
+int lidbox_stats_pool_ragged_fwd(const float* x, long row_stride, const long* seg_offsets, const long* lengths, long B, int C,
+                                 float* out, lidbox_stream_t stream);
+int lidbox_avg_pool_ragged_fwd(const float* x, long row_stride, const long* seg_offsets, const long* lengths, long B, int C,
+                               float* out, lidbox_stream_t stream);
+
 /* lidbox/models/clstm.py:36-42 frequency_attention as used by xvector_freq_attention.py:29, on `rows` = B*T
  * frames of C channels (dense [rows, C]); d_f <= 64 bins of C/d_f consecutive channels.
  * fwd: F_out [rows, d_f] = softmax(logits) (may alias logits); Hw[r, c] = H[r, c] * F_out[r, c / (C/d_f)].

@@ -136,6 +136,10 @@ _SIGS = {
     "lidbox_stats_pool_bwd_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _l, _l, _i, _vp, _l, _l, _vp]),
     "lidbox_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _vp, _vp]),
     "lidbox_avg_pool_bwd": (_i, [_vp, _vp, _i, _i, _i, _l, _l, _i, _vp, _vp]),
+    "lidbox_ragged_pack_rows": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _l, _vp]),
+    "lidbox_ragged_zero_rows": (_i, [_vp, _vp, _l, _i, _i, _vp]),
+    "lidbox_stats_pool_ragged_fwd": (_i, [_vp, _l, _vp, _vp, _l, _i, _vp, _vp]),
+    "lidbox_avg_pool_ragged_fwd": (_i, [_vp, _l, _vp, _vp, _l, _i, _vp, _vp]),
     "lidbox_signal_chunk_plan": (_i, [_l, _i, _i, _i, _i, _vp]),
     "lidbox_frame_rms": (_i, [_vp, _vp, _vp, _i, _l, _i, _vp, _vp]),
     "lidbox_vad_decisions": (_i, [_vp, _vp, _i, _l, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),

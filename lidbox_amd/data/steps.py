@@ -35,7 +35,9 @@ schema (`_feature_extraction_kwargs_to_args`, steps.py:94-104):
 `ragged_batch_size: n` (lidbox_amd only, like `launch_batch` of the signal steps) puts n consecutive elements of ANY lengths into
 one launch of the ragged feature kernel; every element gets what `batch_size: 1` gives it, bit for bit, and the element order is
 kept.  That is the pipeline without signal chunking: VAD leaves every utterance its own length, so `group_by_input_length` finds
-groups of one.  `normalize` has the matching opt-in `ragged: true`.
+groups of one.  `normalize` has the matching opt-in `ragged: true`, and so has `extract_embeddings`: with it, up to `batch_size`
+consecutive `input` tensors of any T go through one ragged model pass per extractor (models/ragged.py), so features, normalisation
+and embeddings of un-chunked utterances all run without one launch per length.
 
 The reference maps this over a tf.data.Dataset (batch -> map -> unbatch); here `ds` is any
 iterable of element dicts holding at least `signal` (1-D float32 tensor or array) and
@@ -543,21 +545,42 @@ def extract_embeddings(ds, config):
     output_shape, best_checkpoint; steps.py:680-681) -- or, additionally, an already built callable: the result of
     `module.as_embedding_extractor(model)`, or a model that has `.embed`, mapping inputs [B, T, C] to embeddings
     [B, D].  The embeddings of several extractors are concatenated on axis 1 (steps.py:693).  Elements of one batch
-    must share the input shape (tf.data's `batch` has the same requirement)."""
+    must share the input shape (tf.data's `batch` has the same requirement).
+    `ragged: true` (lidbox_amd only): up to `batch_size` consecutive elements whose [T, C] inputs may differ in T go through ONE
+    ragged pass per extractor (SequentialTDNN.embed_ragged); order is kept and every element gets what `batch_size: 1` gives it up
+    to rounding.  Every extractor must have a ragged form (`.ragged` of an as_embedding_extractor result, `.embed_ragged` of a
+    model); `no_unbatch` has no meaning without one input shape and is refused."""
+    ragged = bool(config.get("ragged", False))
+    no_unbatch = bool(config.get("no_unbatch", False))
+    if ragged and no_unbatch:
+        raise ValueError("ragged embedding extraction yields elements: no_unbatch needs batches of one input shape")
     extractors = []
     for e in config["extractors"]:
         if isinstance(e, dict):
             from ..models.keras_utils import KerasWrapper
-            fn = KerasWrapper.from_config_as_embedding_extractor_fn(e)
-        else:
-            fn = e.embed if hasattr(e, "embed") else e
+            e = KerasWrapper.from_config_as_embedding_extractor_fn(e)
+        fn = e.embed if hasattr(e, "embed") else e
+        if ragged:
+            fn = getattr(e, "embed_ragged", None) or getattr(e, "ragged", None)
+            if fn is None:
+                raise ValueError("extractor %r has no ragged form (.embed_ragged of a model, .ragged of an embedding extractor)" % (e,))
         if not callable(fn):
             raise ValueError("extractors must be checkpoint configs or callables mapping inputs [B,T,C] to embeddings [B,D]")
         extractors.append(fn)
     logger.info("Using %d extractors", len(extractors))
     batch_size = int(config.get("batch_size", 1))
     logger.info("Batching inputs with batch size %s, extracting embeddings in batches.", batch_size)
-    no_unbatch = bool(config.get("no_unbatch", False))
+    if ragged:
+        for batch in _launch_batches(ds, batch_size):
+            values = [torch.as_tensor(x["input"], dtype=torch.float32) for x in batch]
+            if any(v.dim() != 2 or v.shape[1] != values[0].shape[1] for v in values):
+                raise ValueError("ragged embedding extraction needs [T, C] 'input' tensors with one C")
+            offsets = np.concatenate(([0], np.cumsum([int(v.shape[0]) for v in values])))
+            inputs = torch.cat([v if v.is_cuda else v.cuda() for v in values])
+            embeddings = torch.cat([fn(inputs, offsets) for fn in extractors], dim=1)
+            for i, x in enumerate(batch):
+                yield dict(x, embedding=embeddings[i])
+        return
     for batch in _launch_batches(ds, batch_size):
         inputs = torch.stack([torch.as_tensor(x["input"], dtype=torch.float32) for x in batch])
         if not inputs.is_cuda:

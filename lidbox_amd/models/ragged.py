@@ -1,0 +1,64 @@
+"""
+Host plan of the ragged model pass: where utterances of DIFFERENT lengths live when a causal Conv1D stack runs over all of them in one
+GEMM per layer (no reference counterpart: tf.data batches need one shape).  Pure Python on host integers.
+
+Conv i (i = 0 .. n-1) has kernel k_i and stride s_i, padding "causal", no dilation.  Level i is the input of conv i, level n the
+pooling input.  With
+
+    p_i   = k_i - 1  (i < n),   p_n = 0            causal zero rows ahead of an utterance's frames
+    cum_i = s_i s_{i+1} ... s_{n-1},   cum_n = 1
+    T_{0,b} = frames of utterance b,   T_{i+1,b} = (T_{i,b} - 1) // s_i + 1
+
+utterance b gets  L_b = max_i ceil((p_i + T_{i,b}) / cum_i)  rows at the top level and L_b cum_i rows at level i: its segment starts at
+row off[b] cum_i (off = exclusive prefix sum of L) and holds p_i zero rows, its T_{i,b} frames, then slack.  Level i has
+M_i = off[B] cum_i rows.  Because a level-i segment is exactly s_i times the level-(i+1) segment, ONE rows descriptor with batch = 1
+and row stride s_i C_i over level i lines every utterance's causal windows up with its output rows:
+
+    output row r (counted from p_{i+1} rows into level i+1) reads the level-i rows r s_i .. r s_i + k_i - 1
+    frame t of utterance b at level i+1 is r = off[b] cum_{i+1} + t, whose window starts at level-i row off[b] cum_i + t s_i: the
+    window of padded position t s_i of utterance b
+
+so conv i is one GEMM over M_{i+1} - p_{i+1} rows.  It also writes the p_{i+1} pad rows of utterances 1 .. B-1 (zeroed again right
+behind the GEMM) and the slack rows, which no valid output row ever reads: the last frame's window ends at padded position
+(T_{i+1,b} - 1) s_i + k_i - 1 <= p_i + T_{i,b} - 1.  The last GEMM rows read up to k_i - 1 rows behind M_i, which the buffers have.
+"""
+import numpy as np
+
+
+class RaggedPlan:
+    """pads [n+1], cum [n+1], T [n+1][B] (frames per level and utterance), L [B], off [B+1] (top-level rows, int64) and rows [n+1] = M_i"""
+
+    def __init__(self, pads, cum, T, L, off):
+        self.pads, self.cum, self.T, self.L, self.off = pads, cum, T, L, off
+        self.B = len(L)
+        self.rows = [int(off[-1]) * c for c in cum]
+
+    def seg_offsets(self, i):
+        """start rows of the segments of level i, with the level's end as entry B (int64 [B + 1])"""
+        return self.off * self.cum[i]
+
+    def valid_rows(self, i):
+        return int(self.T[i].sum())
+
+
+def ragged_plan(lengths, convs):
+    """lengths: frames per utterance (each >= 1); convs: (kernel, stride) pairs or objects with .k and .s.  Returns a RaggedPlan."""
+    ks = [(int(c.k), int(c.s)) if hasattr(c, "k") else (int(c[0]), int(c[1])) for c in convs]
+    if any(k < 1 or s < 1 for k, s in ks):
+        raise ValueError("kernel sizes and strides must be >= 1")
+    T0 = np.asarray(lengths, np.int64).reshape(-1)
+    if (T0 < 1).any():
+        raise ValueError("every utterance needs at least one frame, got lengths %s" % T0[T0 < 1][:8].tolist())
+    n = len(ks)
+    pads = [k - 1 for k, _ in ks] + [0]
+    cum = [1] * (n + 1)
+    for i in range(n - 1, -1, -1):
+        cum[i] = cum[i + 1] * ks[i][1]
+    T = [T0]
+    for _, s in ks:
+        T.append((T[-1] - 1) // s + 1)
+    L = np.zeros(len(T0), np.int64)
+    for i in range(n + 1):
+        L = np.maximum(L, -(-(pads[i] + T[i]) // cum[i]))
+    off = np.concatenate(([0], np.cumsum(L))).astype(np.int64)
+    return RaggedPlan(pads, cum, T, L, off)

@@ -283,6 +283,42 @@ class _Workspace(Workspace):
         return self.act[0][:, self.pads[0]:, :]
 
 
+class _RaggedWorkspace:
+    """The device buffers of the ragged pass (models/ragged.py), sized by capacity: `cap_rows` top-level rows and `cap_B`
+    utterances.  act[i] is level i: cap_rows * cum_i rows of C_i floats plus the k_i - 1 rows the last GEMM rows read behind them.
+    Zero-initialised; a pass writes what it reads (lidbox_ragged_pack_rows every level-0 row, the GEMMs every row behind the first
+    pad, lidbox_ragged_zero_rows every pad), so rows left over from a larger earlier pass are never read by a valid output row."""
+
+    def __init__(self, model):
+        self.cap_rows = self.cap_B = self.B = 0
+        self.gemm_ws = torch.empty(16, dtype=torch.uint8, device=model.device)
+
+    def reserve(self, model, top_rows, B):
+        """room for top_rows top-level rows and B utterances: a capacity that is exceeded becomes at least half as large again
+        and only its own buffers are replaced (the level buffers for rows, the pooled / head buffers for utterances)"""
+        f32 = dict(dtype=torch.float32, device=model.device)
+        convs = model.convs
+        chans = [model.input_dim] + [c.filters for c in convs]
+        if top_rows > self.cap_rows:
+            self.cap_rows = max(int(top_rows), self.cap_rows + self.cap_rows // 2)
+            cum = [1] * len(chans)
+            for i in range(len(convs) - 1, -1, -1):
+                cum[i] = cum[i + 1] * convs[i].s
+            tails = [c.k - 1 for c in convs] + [0]
+            self.act = [torch.zeros((self.cap_rows * cum[i] + tails[i], chans[i]), **f32) for i in range(len(chans))]
+        if B > self.cap_B:
+            self.cap_B = max(int(B), self.cap_B + self.cap_B // 2)
+            P = 2 * chans[-1] if model.pool == "stats" else chans[-1]
+            self.pooled = torch.zeros((self.cap_B, P), **f32)
+            self.h = [torch.zeros((self.cap_B, d.units), **f32) for d in model.denses]
+            self.logp = torch.zeros((self.cap_B, model.denses[-1].units), **f32)
+            self.emb = torch.zeros((self.cap_B, model.denses[0].units), **f32)
+
+    def reserve_gemm_ws(self, model, nbytes):
+        if nbytes > self.gemm_ws.numel():
+            self.gemm_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=model.device)
+
+
 class SequentialTDNN(FlatParams):
     """convs -> pool -> denses -> log_softmax, parameters in one flat buffer (accessors and workspace cache: models/flat.py)."""
 
@@ -744,6 +780,12 @@ class SequentialTDNN(FlatParams):
         else:
             fn = lib.lidbox_stats_pool_fwd if self.pool == "stats" else lib.lidbox_avg_pool_fwd
             nv.check(fn(nv.ptr(last), ws.B, T, C, T * C, C, nv.ptr(ws.pooled), st))
+        return self._forward_head(ws, upto_embedding, stop_before_output)
+
+    def _forward_head(self, ws, upto_embedding=False, stop_before_output=False):
+        """the dense layers and the output activation on the ws.B rows of ws.pooled (the dense and the ragged pass share it)"""
+        st = nv.current_stream()
+        lib = nv.lib
         x, din = ws.pooled, ws.pooled.shape[1]
         for j, d in enumerate(self.denses):
             if stop_before_output and j == len(self.denses) - 1:
@@ -1136,6 +1178,94 @@ class SequentialTDNN(FlatParams):
 
     predict = __call__
 
+    # ------------------------------------------------------------------ ragged pass (inference, float32)
+    def ragged_refusal(self):
+        """why this model has no ragged pass (None: it has one).  The layout of models/ragged.py is that of a plain causal,
+        undilated Conv1D stack in front of the pooling."""
+        if self.frontend:
+            return "the ragged pass does not run a 2-D front-end"
+        if self.attention is not None:
+            return "the ragged pass does not run frequency attention"
+        if self.compute_dtype != "float32":
+            return "the ragged pass computes in float32 only, this model has compute_dtype=%r" % self.compute_dtype
+        for c in self.convs:
+            if c.padding != "causal" or c.d > 1:
+                return "the ragged pass needs causal, undilated convolutions; %s has padding=%r, dilation_rate=%d" % (c.name, c.padding, c.d)
+        if type(self)._before_conv is not SequentialTDNN._before_conv:
+            return "the ragged pass does not run the layers %s puts between its convolutions (_before_conv)" % type(self).__name__
+        return None
+
+    def ragged_workspace(self, top_rows, B):
+        """the model's one _RaggedWorkspace, with room for top_rows top-level rows and B utterances (_RaggedWorkspace.reserve)"""
+        ws = getattr(self, "_rws", None)
+        if ws is None:
+            ws = self._rws = _RaggedWorkspace(self)
+        ws.reserve(self, top_rows, B)
+        return ws
+
+    def forward_ragged(self, X, row_offsets, upto_embedding=False):
+        """Inference on utterances of different lengths in one pass.  X [total_T, C] float32, contiguous, on the HIP device;
+        utterance b = rows row_offsets[b] .. row_offsets[b + 1] (host array of B + 1 entries: the conventions of
+        features.cmvn_ragged).  Returns a view of the workspace: the model output [B, num_outputs] or, upto_embedding, the
+        embedding [B, D] -- what the dense pass gives each utterance alone, up to the rounding of another GEMM / pooling path.
+        pack -> per conv one GEMM over all utterances (+ the pad-row repair) -> ragged pooling -> the dense head."""
+        reason = self.ragged_refusal()
+        if reason:
+            raise ValueError(reason)
+        X = nv.require_gpu_tensor(X, "X", torch.float32)
+        if X.dim() != 2 or X.shape[1] != self.input_dim or not X.is_contiguous():
+            raise ValueError("expected a contiguous input [total_T, %d], got %s" % (self.input_dim, tuple(X.shape)))
+        ro = np.ascontiguousarray(np.asarray(row_offsets, np.int64).reshape(-1))
+        if len(ro) < 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or int(ro[-1]) != X.shape[0]:
+            raise ValueError("row_offsets must rise from 0 to the %d rows of X" % X.shape[0])
+        lengths = np.diff(ro)
+        if (lengths < 1).any():
+            raise ValueError("utterance %d has length 0: every utterance needs at least one frame" % int(np.flatnonzero(lengths < 1)[0]))
+        from .ragged import ragged_plan
+        B, n = len(lengths), len(self.convs)
+        with torch.cuda.device(self.device):
+            if B == 0:
+                D = self.denses[0].units if upto_embedding else self.denses[-1].units
+                return torch.zeros((0, D), dtype=torch.float32, device=self.device)
+            plan = ragged_plan(lengths, self.convs)
+            ws = self.ragged_workspace(int(plan.off[-1]), B)
+            ws.B = B
+            chans = [self.input_dim] + [c.filters for c in self.convs]
+            g, need = self.gemm, 16
+            for i, c in enumerate(self.convs):
+                need = max(need, g.rows_workspace(plan.rows[i + 1] - plan.pads[i + 1], c.filters, c.k * chans[i]))
+            din = ws.pooled.shape[1]
+            for d in self.denses:
+                need = max(need, self.dense_gemm.rows_workspace(B, d.units, din))
+                din = d.units
+            ws.reserve_gemm_ws(self, need)
+            # one upload: the segment offsets of every level, the source offsets, the pooling lengths
+            host = np.concatenate([plan.seg_offsets(i) for i in range(n + 1)] + [ro, plan.T[n]])
+            dev = torch.from_numpy(host).to(self.device)
+            seg = [ctypes.c_void_p(dev.data_ptr() + 8 * i * (B + 1)) for i in range(n + 3)]
+            st, lib = nv.current_stream(), nv.lib
+            k0 = self.convs[0].k if n else 1
+            nv.check(lib.lidbox_ragged_pack_rows(nv.ptr(X), seg[n + 1], nv.ptr(ws.act[0]), seg[0], B, chans[0], plan.pads[0], k0 - 1, st))
+            for i, c in enumerate(self.convs):
+                M, p, Co = plan.rows[i + 1] - plan.pads[i + 1], plan.pads[i + 1], c.filters
+                nv.check(g.nn(_rows(ws.act[i].data_ptr(), 0, c.s * chans[i], 1, M), self._p(c.name + ".W"), Co,
+                              _rows(ws.act[i + 1].data_ptr() + 4 * p * Co, 0, Co, 1, M), c.k * chans[i], Co,
+                              nv.EPI_BIAS_RELU if c.relu else nv.EPI_BIAS, self._p(c.name + ".b"),
+                              nv.ptr(ws.gemm_ws), ws.gemm_ws.numel(), st))
+                if p > 0:
+                    nv.check(lib.lidbox_ragged_zero_rows(nv.ptr(ws.act[i + 1]), seg[i + 1], B, Co, p, st))
+            fn = lib.lidbox_stats_pool_ragged_fwd if self.pool == "stats" else lib.lidbox_avg_pool_ragged_fwd
+            nv.check(fn(nv.ptr(ws.act[n]), chans[n], seg[n], seg[n + 2], B, chans[n], nv.ptr(ws.pooled), st))
+            return self._forward_head(ws, upto_embedding)[:B]
+
+    def predict_ragged(self, X, row_offsets):
+        """log-probs (or what output_activation makes) [B, num_outputs] of B utterances of different lengths (a fresh tensor)"""
+        return self.forward_ragged(X, row_offsets).clone()
+
+    def embed_ragged(self, X, row_offsets):
+        """`embed` for B utterances of different lengths: [B, D] (a fresh tensor)"""
+        return self.forward_ragged(X, row_offsets, upto_embedding=True).clone()
+
 
 class EmbeddingExtractor:
     """Result of `as_embedding_extractor(model)` (reference xvector.py:70-73 / cnn.py:19-22)."""
@@ -1146,3 +1276,7 @@ class EmbeddingExtractor:
 
     def __call__(self, x, training=False):
         return self.model.embed(x)
+
+    def ragged(self, X, row_offsets):
+        """the embeddings [B, D] of B utterances of different lengths (SequentialTDNN.embed_ragged)"""
+        return self.model.embed_ragged(X, row_offsets)

@@ -2,6 +2,7 @@
 Counterpart of the lidbox/util.py entries around prediction and scoring:
 
   predictions_to_dataframe, predict_with_model   reference util.py:17-38
+  predict_ragged_with_model                      no counterpart: elements of any length, one ragged model pass per launch batch
   chunk_parent_id, merge_chunk_predictions       reference util.py:41-57   (chunk rows averaged on the device)
   classification_report                          reference util.py:60-105
 
@@ -36,6 +37,37 @@ def predict_with_model(model, ds, predict_fn=None):
         for i, p in zip(bid, pred):                                                  # unbatch, :33-35
             ids.append(i.decode("utf-8") if isinstance(i, bytes) else str(i))
             predictions.append(p)
+    return predictions_to_dataframe(ids, predictions)
+
+
+def predict_ragged_with_model(model, ds, launch_batch=256):
+    """`predict_with_model` for utterances of different lengths (no reference counterpart): `ds` yields ELEMENTS, dicts with `id` and
+    `input` ([T, C], any T); up to `launch_batch` consecutive ones go through one ragged pass (`model.predict_ragged`).  Returns the
+    DataFrame `predict_with_model` returns."""
+    launch_batch = int(launch_batch)
+    if launch_batch < 1:
+        raise ValueError("launch_batch must be at least 1")
+    ids, predictions, batch = [], [], []
+
+    def flush():
+        values = [torch.as_tensor(x["input"], dtype=torch.float32) for x in batch]
+        if any(v.dim() != 2 or v.shape[1] != values[0].shape[1] for v in values):
+            raise ValueError("ragged prediction needs [T, C] 'input' tensors with one C")
+        offsets = np.concatenate(([0], np.cumsum([int(v.shape[0]) for v in values])))
+        inputs = torch.cat([v if v.is_cuda else v.cuda() for v in values])
+        pred = model.predict_ragged(inputs, offsets).detach().cpu().numpy()
+        for x, p in zip(batch, pred):
+            i = x["id"]
+            ids.append(i.decode("utf-8") if isinstance(i, bytes) else str(i))
+            predictions.append(p)
+        del batch[:]
+
+    for x in ds:
+        batch.append(x)
+        if len(batch) == launch_batch:
+            flush()
+    if batch:
+        flush()
     return predictions_to_dataframe(ids, predictions)
 
 
