@@ -427,6 +427,42 @@ int lidbox_gemm_bf16s_tn_last_pp(void);
  * stride is a whole number of row strides -- frame1's wgrad (k = 5, 40 channels: K1 = 200).  LIDBOX_GEMM16_TN_KRES=0 / 1: never /
  * whenever the operands allow. */
 int lidbox_gemm_bf16s_tn_last_kres(void);
+/* The bf16 families' planner as a query (tests, profiling tools): launches nothing and needs no device.  It runs the functions the
+ * launches run and reports what a call with these arguments would do; pointers are only tested for alignment and NULL.
+ *   kind      LIDBOX_Q16_NN / _NT / _TN: lidbox_gemm_bf16_nn / _nt / _tn; LIDBOX_Q16S_NT: lidbox_gemm_bf16s_nt(_carry); LIDBOX_Q16S_TN:
+ *             lidbox_gemm_bf16s_tn(_partial)
+ *   A         the row operand; B: rows kinds {base = the weight, row_stride = ldb}, wgrads the second row operand
+ *   C         rows kinds the output descriptor (base NULL: shadow only); wgrads {base = the output, row_stride = ldc}
+ *   K, N      wgrads: K = K1;  aux: wgrads the bias gradient (NULL: none);  njobs: non-empty carried jobs (LIDBOX_Q16S_NT)
+ * out12 = {kernel (LIDBOX_K16_*; LIDBOX_K16_REFUSED: the call returns LIDBOX_E_INVALID for its alignment), tile rows, tile columns,
+ *          stages (as lidbox_gemm_bf16s_last_variant), splits / slices, k_per_split / rows_per_split, m_main of the tail split (0: none),
+ *          splits and k_per_split of the rows behind m_main, the reduce that follows (LIDBOX_R16_*), wgrads: 1 if the workspace
+ *          holds the slices, K1-resident wgrad: utterances per slice}.
+ * lidbox_gemm_bf16_last_plan: out4 = {kernel, splits / slices, k_per_split / rows_per_split (K1-resident wgrad: utterances per
+ * slice), m_main} of the calling thread's most recent launch of either bf16 family. */
+enum {
+    LIDBOX_Q16_NN = 0, LIDBOX_Q16_NT = 1, LIDBOX_Q16_TN = 2, LIDBOX_Q16S_NT = 3, LIDBOX_Q16S_TN = 4
+};
+enum {
+    LIDBOX_K16_REFUSED = -1, LIDBOX_K16_NONE = 0,
+    LIDBOX_K16_ROWS = 1,        /* gemm16_rows_kernel */
+    LIDBOX_K16_TN = 2,          /* gemm16_tn_kernel */
+    LIDBOX_K16S_ROWS = 3,       /* gemm16s_rows_kernel (register-staged) */
+    LIDBOX_K16S_DMA = 4,        /* gemm16s_rows_dma_kernel<bm, bn, stages> */
+    LIDBOX_K16S_PP = 5,         /* gemm16s_rows_pp_kernel<bn, sub> (or the two-problem grid) */
+    LIDBOX_K16S_KRES13 = 6,     /* gemm16s_rows_kres_kernel<13> */
+    LIDBOX_K16S_KRES0 = 7,      /* gemm16s_rows_kres_kernel<0> */
+    LIDBOX_K16S_TN = 8,         /* gemm16s_tn_kernel */
+    LIDBOX_K16S_TN_PP = 9,      /* gemm16s_tn_pp_kernel */
+    LIDBOX_K16S_TN_KRES = 10    /* gemm16s_tn_kres_kernel */
+};
+enum {
+    LIDBOX_R16_NONE = 0, LIDBOX_R16_ROWS = 1 /* rows_reduce_kernel */, LIDBOX_R16_JOB4 = 2 /* the 16-byte reduce job */,
+    LIDBOX_R16_SCALAR = 3 /* splitk_reduce_kernel, launched by the wgrad call itself */
+};
+int lidbox_gemm_bf16_plan_query(int kind, lidbox_rows_t A, lidbox_rows_t B, lidbox_rows_out_t C, const void* C16, int K, int N,
+                                int epilogue, const void* aux, int njobs, const void* workspace, size_t workspace_bytes, long* out12);
+int lidbox_gemm_bf16_last_plan(long* out4);
 /* All bf16 weight shadows of a model in ONE launch (once per train step, after the optimizer): flat16[i] = bf16(flat[i]) for
  * the n parameters, and for each listed row-major [rows][cols] matrix at flat + offset a bf16 image at dst with its own
  * leading dimension: transposed ([cols][rows]: a Keras Conv1D kernel [k*C_in][C_out] -> the K-inner [C_out][k*C_in] operand

@@ -946,14 +946,51 @@ TnPpPlan plan_tn16_pp(long M, int K1, int N) {
 const char* const ALIGN_MSG =
     "bf16 path needs 16-byte aligned operands and K, N, leading dimensions and row strides that are multiples of 4";
 
+// Tail quantisation (as in gemm.hip): `slots` workgroups are resident, and the last partial round of a launch
+// runs at the pace of a full one.  When the tiles beyond the last whole round are few (<= a quarter round), the
+// launch covers the row prefix that is a whole number of rounds and the few remaining rows go to a second launch
+// split along K (each of its workgroups does 1/splits of a tile, so it costs a fraction of a round).
+struct Rows16Tail {
+    long m_main;                        // 0: one launch over all rows
+    Rows16Plan rem;                     // the plan of rows [m_main, M)
+};
+
+Rows16Tail plan_tail16(const Rows16Plan& pl, long M, int N, int K, size_t ws_bytes, int BK, long slots) {
+    Rows16Tail t{0, Rows16Plan{1, K}};
+    const int tiles_n = (int)lbx_cdiv(N, BT);
+    const long tiles = lbx_cdiv(M, BT) * tiles_n;
+    if (pl.splits == 1 && tiles > slots && K >= TAIL_MIN_K) {   // short K: the extra launch costs more than the round
+        const long rounds = tiles / slots, rem_tiles = tiles - rounds * slots;
+        const long main_tiles_m = rounds * slots / tiles_n;
+        const long m_main = main_tiles_m * BT, m_rem = M - m_main;
+        if (rounds >= TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
+            const Rows16Plan rp = plan_rows16(m_rem, N, K, ws_bytes, BK);
+            if (rp.splits > 1) return Rows16Tail{m_main, rp};
+        }
+    }
+    return t;
+}
+
+// what the calling thread's last bf16 GEMM launched (lidbox_gemm_bf16_last_plan): {kernel (LIDBOX_K16_*), splits or slices,
+// k_per_split or rows_per_split, m_main of a tail split (0: none)}
+thread_local long g16_last_plan[4] = {0, 0, 0, 0};
+inline void record_plan16(int kernel, long splits, long per_split, long m_main) {
+    g16_last_plan[0] = kernel; g16_last_plan[1] = splits; g16_last_plan[2] = per_split; g16_last_plan[3] = m_main;
+}
+
+// the alignment the fp32-source row kernels need (lidbox_gemm_bf16_nn / _nt)
+bool rows16_operands_ok(bool b_kinner, const lidbox_rows_t& A, const void* Bm, long ldb, const lidbox_rows_out_t& Cd, int K, int N,
+                        const void* ws) {
+    const lidbox_rows_t Cin{Cd.base, Cd.batch_stride, Cd.row_stride, Cd.batch, Cd.rows_per_batch};
+    return rows_aligned(A) && rows_aligned(Cin) && K % 4 == 0 && aligned16(Bm) && ldb % 4 == 0 && (b_kinner || N % 4 == 0) && aligned16(ws);
+}
+
 template <bool B_KINNER>
 int launch_rows16(const char* fn, lidbox_rows_t A, const float* Bm, long ldb, lidbox_rows_out_t Cd, int K, int N, int epi,
                   const float* aux, void* ws, size_t ws_bytes, hipStream_t st) {
     const long M = (long)A.batch * A.rows_per_batch;
-    if (M == 0 || N == 0) return LIDBOX_OK;
-    const lidbox_rows_t Cin{Cd.base, Cd.batch_stride, Cd.row_stride, Cd.batch, Cd.rows_per_batch};
-    if (!(rows_aligned(A) && rows_aligned(Cin) && K % 4 == 0 && aligned16(Bm) && ldb % 4 == 0 &&
-          (B_KINNER || N % 4 == 0) && aligned16(ws))) {
+    if (M == 0 || N == 0) { record_plan16(LIDBOX_K16_NONE, 0, 0, 0); return LIDBOX_OK; }
+    if (!rows16_operands_ok(B_KINNER, A, Bm, ldb, Cd, K, N, ws)) {
         lidbox_set_error("%s: invalid argument: %s", fn, ALIGN_MSG);
         return LIDBOX_E_INVALID;
     }
@@ -977,23 +1014,12 @@ int launch_rows16(const char* fn, lidbox_rows_t A, const float* Bm, long ldb, li
         }
         return LIDBOX_OK;
     };
-    // Tail quantisation (as in gemm.hip): two workgroups per CU = 512 slots, and the last partial round of a launch
-    // runs at the pace of a full one.  When the tiles beyond the last whole round are few (<= a quarter round), the
-    // launch covers the row prefix that is a whole number of rounds and the few remaining rows go to a second launch
-    // split along K (each of its workgroups does 1/splits of a tile, so it costs a fraction of a round).
-    const long slots = 2 * NUM_CU;
-    const long tiles = lbx_cdiv(M, BT) * tiles_n;
-    if (pl.splits == 1 && tiles > slots && K >= TAIL_MIN_K) {   // short K: the extra launch costs more than the round
-        const long rounds = tiles / slots, rem_tiles = tiles - rounds * slots;
-        const long main_tiles_m = rounds * slots / tiles_n;
-        const long m_main = main_tiles_m * BT, m_rem = M - m_main;
-        if (rounds >= TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
-            const Rows16Plan rp = plan_rows16(m_rem, N, K, ws ? ws_bytes : 0);
-            if (rp.splits > 1) {
-                if (int rc = launch_range(0, m_main, pl)) return rc;
-                return launch_range(m_main, M, rp);
-            }
-        }
+    // two workgroups per CU = 512 slots (plan_tail16)
+    const Rows16Tail tail = plan_tail16(pl, M, N, K, ws ? ws_bytes : 0, 32, 2 * NUM_CU);
+    record_plan16(LIDBOX_K16_ROWS, pl.splits, pl.k_per_split, tail.m_main);
+    if (tail.m_main > 0) {
+        if (int rc = launch_range(0, tail.m_main, pl)) return rc;
+        return launch_range(tail.m_main, M, tail.rem);
     }
     return launch_range(0, M, pl);
 }
@@ -1169,6 +1195,65 @@ inline long carry_cap16() {
     return 96;
 }
 
+// the alignment the storage row kernels need (lidbox_gemm_bf16s_nt and its carry / pair forms)
+bool rows16s_operands_ok(const lidbox_rows_t& A, const void* B16, long ldb, const lidbox_rows_out_t& Cd, const void* C16, int K, const void* ws) {
+    const lidbox_rows_t Cin{Cd.base, Cd.batch_stride, Cd.row_stride, Cd.batch, Cd.rows_per_batch};
+    const bool a_ok = aligned16(A.base) && A.row_stride % 8 == 0 && (A.batch == 1 || A.batch_stride % 8 == 0);
+    return a_ok && rows_aligned(Cin) && K % 8 == 0 && aligned16(B16) && ldb % 8 == 0 && aligned16(ws) &&
+           (C16 == nullptr || (((uintptr_t)C16) & 1) == 0);
+}
+
+// Which kernel a storage rows call runs and how it is cut (launch_rows16s follows it; lidbox_gemm_bf16_plan_query reports it).
+// epi: without LIDBOX_EPI_MASK_BF16; carries: the launch has pending reduce jobs in its leading workgroups; ws_bytes: 0 without a
+// workspace.  Pointers are only tested for alignment and NULL.
+struct Rows16sPlan {
+    int kernel = LIDBOX_K16_NONE;       // LIDBOX_K16S_KRES13 | _KRES0 | _DMA | _PP | _ROWS
+    Dma16Choice dc;                     // _DMA, _PP
+    Rows16Plan pl{1, 0};                // _ROWS
+    Rows16Tail tail{0, Rows16Plan{1, 0}};
+};
+
+Rows16sPlan plan_rows16s(const lidbox_rows_t& A, long ldb, const lidbox_rows_out_t& Cd, const void* C16, int K, int N, int epi, bool has_mask16,
+                         bool carries, size_t ws_bytes) {
+    Rows16sPlan d;
+    const long M = (long)A.batch * A.rows_per_batch;
+    {
+        // short contraction over overlapping windows of short utterances (frame1's forward): both operands resident in LDS
+        // (gemm16_kres.h).  LIDBOX_GEMM16S_KRES=0 | 1: never | whenever it can run (tuning aid)
+        int mode = -1;
+        if (const char* e = getenv("LIDBOX_GEMM16S_KRES")) mode = atoi(e);
+        const bool epi_ok = epi == LIDBOX_EPI_NONE || epi == LIDBOX_EPI_BIAS || epi == LIDBOX_EPI_BIAS_RELU || epi == LIDBOX_EPI_RELU;
+        // vector stores: whole 8-column chunks on 16-byte (fp32) / 8-byte (shadow) boundaries
+        const bool c_ok = ((Cd.batch == A.batch && Cd.rows_per_batch == A.rows_per_batch) || Cd.batch == 1) && N % 8 == 0 &&
+                          Cd.row_stride % 4 == 0 && (Cd.batch == 1 || Cd.batch_stride % 4 == 0) && aligned16(Cd.base) &&
+                          (((uintptr_t)C16) & 7) == 0;
+        const int tiles_n = (int)lbx_cdiv(N, KRES_BN);
+        const double a_span = ((double)(A.batch - 1) * (double)A.batch_stride + (double)A.rows_per_batch * (double)A.row_stride + K) * 2.0;
+        const bool can = mode != 0 && !carries && epi_ok && c_ok && !has_mask16 && kres_applies(A, K, N) && A.batch_stride >= 0 &&
+                         a_span < 4.0e9 && tiles_n <= NUM_CU &&
+                         ((double)(A.rows_per_batch - 1) * (double)A.row_stride + K) * 2.0 < 2.0e9;
+        // worth it when the launch is a store stream: windows that overlap (row stride < K) and enough utterances to keep every
+        // CU's workgroup busy for a few tiles
+        if (can && (mode == 1 || (A.row_stride * 2 <= K && (long)A.batch * tiles_n >= 2 * NUM_CU))) {
+            d.kernel = (K + 15) / 16 == 13 ? LIDBOX_K16S_KRES13 : LIDBOX_K16S_KRES0;      // <13>: frame1 of the x-vector, K = 200
+            return d;
+        }
+    }
+    const Dma16Choice dc = choose_dma16(M, N, K, ws_bytes, Cd.base != nullptr);
+    // 32-bit byte offsets per lane inside the kernel: the operands' extents must fit
+    const double a_ext = ((double)(A.batch - 1) * (double)A.batch_stride + (double)A.rows_per_batch * (double)A.row_stride + K) * 2.0;
+    const double b_ext = ((double)N * (double)ldb + K) * 2.0;
+    if (dc.bm != 0 && a_ext < 4.0e9 && b_ext < 4.0e9) {
+        d.kernel = dc.bm == 256 ? LIDBOX_K16S_PP : LIDBOX_K16S_DMA;
+        d.dc = dc;
+        return d;
+    }
+    d.kernel = LIDBOX_K16S_ROWS;
+    d.pl = plan_rows16(M, N, K, ws_bytes, BKS);
+    d.tail = plan_tail16(d.pl, M, N, K, ws_bytes, BKS, (long)WAVES_S * NUM_CU);
+    return d;
+}
+
 // jobs / njobs: pending wgrad reduces this launch carries in its leading workgroups (the first kernel launched takes them)
 int launch_rows16s(const char* fn, lidbox_rows_t A, const void* B16, long ldb, lidbox_rows_out_t Cd, void* C16, int K, int N,
                    int epi, const float* aux, void* ws, size_t ws_bytes, hipStream_t st, const unsigned short* mask16,
@@ -1178,12 +1263,10 @@ int launch_rows16s(const char* fn, lidbox_rows_t A, const void* B16, long ldb, l
     if (njobs > 0) rj = pack_carry(jobs, njobs, carry_cap16());
     if (M == 0 || N == 0) {
         if (rj.total) hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(rj.total), dim3(256), 0, st, rj);
+        record_plan16(LIDBOX_K16_NONE, 0, 0, 0);
         return LIDBOX_OK;
     }
-    const lidbox_rows_t Cin{Cd.base, Cd.batch_stride, Cd.row_stride, Cd.batch, Cd.rows_per_batch};
-    const bool a_ok = aligned16(A.base) && A.row_stride % 8 == 0 && (A.batch == 1 || A.batch_stride % 8 == 0);
-    if (!(a_ok && rows_aligned(Cin) && K % 8 == 0 && aligned16(B16) && ldb % 8 == 0 && aligned16(ws) &&
-          (C16 == nullptr || (((uintptr_t)C16) & 1) == 0))) {
+    if (!rows16s_operands_ok(A, B16, ldb, Cd, C16, K, ws)) {
         lidbox_set_error("%s: invalid argument: bf16-storage operands need 16-byte aligned bases and K, ldb, row and batch "
                          "strides (in bf16 elements) that are multiples of 8", fn);
         return LIDBOX_E_INVALID;
@@ -1191,62 +1274,42 @@ int launch_rows16s(const char* fn, lidbox_rows_t A, const void* B16, long ldb, l
     const RowsOutD Co_{Cd.base, Cd.batch_stride, Cd.row_stride, Cd.batch, Cd.rows_per_batch};
     const RowsH Ah_{(const __bf16*)A.base, A.batch_stride, A.row_stride, A.batch, A.rows_per_batch};
     const RowsH Bh_{(const __bf16*)B16, 0, ldb, 1, 0};
-    {
-        // short contraction over overlapping windows of short utterances (frame1's forward): both operands resident in LDS
-        // (gemm16_kres.h).  LIDBOX_GEMM16S_KRES=0 | 1: never | whenever it can run (tuning aid)
-        {
-            int mode = -1;
-            if (const char* e = getenv("LIDBOX_GEMM16S_KRES")) mode = atoi(e);
-            const int base_epi = epi & ~LIDBOX_EPI_MASK_BF16;
-            const bool epi_ok = base_epi == LIDBOX_EPI_NONE || base_epi == LIDBOX_EPI_BIAS || base_epi == LIDBOX_EPI_BIAS_RELU || base_epi == LIDBOX_EPI_RELU;
-            // vector stores: whole 8-column chunks on 16-byte (fp32) / 8-byte (shadow) boundaries
-            const bool c_ok = ((Cd.batch == A.batch && Cd.rows_per_batch == A.rows_per_batch) || Cd.batch == 1) && N % 8 == 0 &&
-                              Cd.row_stride % 4 == 0 && (Cd.batch == 1 || Cd.batch_stride % 4 == 0) && aligned16(Cd.base) &&
-                              (((uintptr_t)C16) & 7) == 0;
-            const int tiles_n = (int)lbx_cdiv(N, KRES_BN);
-            const double a_span = ((double)(A.batch - 1) * (double)A.batch_stride + (double)A.rows_per_batch * (double)A.row_stride + K) * 2.0;
-            const bool can = mode != 0 && rj.total == 0 && epi_ok && c_ok && mask16 == nullptr && kres_applies(A, K, N) && A.batch_stride >= 0 &&
-                             a_span < 4.0e9 && tiles_n <= NUM_CU &&
-                             ((double)(A.rows_per_batch - 1) * (double)A.row_stride + K) * 2.0 < 2.0e9;
-            // worth it when the launch is a store stream: windows that overlap (row stride < K) and enough utterances to keep every
-            // CU's workgroup busy for a few tiles
-            if (can && (mode == 1 || (A.row_stride * 2 <= K && (long)A.batch * tiles_n >= 2 * NUM_CU))) {
-                int dev = 0;
-                LBX_HIP(hipGetDevice(&dev));
-                static std::atomic<unsigned long long> kres_attr{0};
-                if (dev < 64 && !((kres_attr.load() >> dev) & 1ull)) {
-                    LBX_HIP(hipFuncSetAttribute((const void*)gemm16s_rows_kres_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, KRES_LDS_BYTES));
-                    LBX_HIP(hipFuncSetAttribute((const void*)gemm16s_rows_kres_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, KRES_LDS_BYTES));
-                    kres_attr.fetch_or(1ull << dev);
-                }
-                const int blocks = (int)lbx_cdiv(A.rows_per_batch, KRES_ROWS);
-                const long nunits = (long)A.batch * blocks;
-                long nstreams = NUM_CU / tiles_n;                               // one workgroup per CU (146 KB of LDS)
-                if (nstreams > lbx_cdiv(nunits, (long)KRES_WAVES)) nstreams = lbx_cdiv(nunits, (long)KRES_WAVES);
-                if (nstreams < 1) nstreams = 1;
-                g16_last_variant[0] = 1; g16_last_variant[1] = KRES_BN; g16_last_variant[2] = 1;      // {1, 64, 1}: the K-resident kernel
-                if ((K + 15) / 16 == 13)                                        // frame1 of the x-vector: K = 200
-                    hipLaunchKernelGGL(gemm16s_rows_kres_kernel<13>, dim3((unsigned)(tiles_n * nstreams)), dim3(64 * KRES_WAVES), KRES_LDS_BYTES, st, Ah_,
-                                       Bh_, Co_, (unsigned short*)C16, K, N, base_epi, aux, tiles_n, (int)nstreams, blocks, nunits);
-                else
-                    hipLaunchKernelGGL(gemm16s_rows_kres_kernel<0>, dim3((unsigned)(tiles_n * nstreams)), dim3(64 * KRES_WAVES), KRES_LDS_BYTES, st, Ah_,
-                                       Bh_, Co_, (unsigned short*)C16, K, N, base_epi, aux, tiles_n, (int)nstreams, blocks, nunits);
-                LBX_LAUNCH_OK();
-                return LIDBOX_OK;
-            }
+    const Rows16sPlan d = plan_rows16s(A, ldb, Cd, C16, K, N, epi & ~LIDBOX_EPI_MASK_BF16, mask16 != nullptr, rj.total != 0, ws ? ws_bytes : 0);
+    if (d.kernel == LIDBOX_K16S_KRES13 || d.kernel == LIDBOX_K16S_KRES0) {
+        const int base_epi = epi & ~LIDBOX_EPI_MASK_BF16;
+        const int tiles_n = (int)lbx_cdiv(N, KRES_BN);
+        int dev = 0;
+        LBX_HIP(hipGetDevice(&dev));
+        static std::atomic<unsigned long long> kres_attr{0};
+        if (dev < 64 && !((kres_attr.load() >> dev) & 1ull)) {
+            LBX_HIP(hipFuncSetAttribute((const void*)gemm16s_rows_kres_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, KRES_LDS_BYTES));
+            LBX_HIP(hipFuncSetAttribute((const void*)gemm16s_rows_kres_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, KRES_LDS_BYTES));
+            kres_attr.fetch_or(1ull << dev);
         }
-        const Dma16Choice dc = choose_dma16(M, N, K, ws ? ws_bytes : 0, Cd.base != nullptr);
-        // 32-bit byte offsets per lane inside the kernel: the operands' extents must fit
-        const double a_ext = ((double)(A.batch - 1) * (double)A.batch_stride + (double)A.rows_per_batch * (double)A.row_stride + K) * 2.0;
-        const double b_ext = ((double)N * (double)ldb + K) * 2.0;
-        g16_last_variant[0] = g16_last_variant[1] = g16_last_variant[2] = 0;
-        if (dc.bm != 0 && a_ext < 4.0e9 && b_ext < 4.0e9) {
-            g16_last_variant[0] = dc.bm; g16_last_variant[1] = dc.bn; g16_last_variant[2] = dc.stages;
-        }
-        if (dc.bm != 0 && a_ext < 4.0e9 && b_ext < 4.0e9)
-            return launch_rows16s_dma(dc, Ah_, Bh_, Co_, (unsigned short*)C16, (float*)ws, M, K, N, epi, aux, mask16, st, rj);
+        const int blocks = (int)lbx_cdiv(A.rows_per_batch, KRES_ROWS);
+        const long nunits = (long)A.batch * blocks;
+        long nstreams = NUM_CU / tiles_n;                               // one workgroup per CU (146 KB of LDS)
+        if (nstreams > lbx_cdiv(nunits, (long)KRES_WAVES)) nstreams = lbx_cdiv(nunits, (long)KRES_WAVES);
+        if (nstreams < 1) nstreams = 1;
+        g16_last_variant[0] = 1; g16_last_variant[1] = KRES_BN; g16_last_variant[2] = 1;      // {1, 64, 1}: the K-resident kernel
+        record_plan16(d.kernel, 1, K, 0);
+        if (d.kernel == LIDBOX_K16S_KRES13)                             // frame1 of the x-vector: K = 200
+            hipLaunchKernelGGL(gemm16s_rows_kres_kernel<13>, dim3((unsigned)(tiles_n * nstreams)), dim3(64 * KRES_WAVES), KRES_LDS_BYTES, st, Ah_,
+                               Bh_, Co_, (unsigned short*)C16, K, N, base_epi, aux, tiles_n, (int)nstreams, blocks, nunits);
+        else
+            hipLaunchKernelGGL(gemm16s_rows_kres_kernel<0>, dim3((unsigned)(tiles_n * nstreams)), dim3(64 * KRES_WAVES), KRES_LDS_BYTES, st, Ah_,
+                               Bh_, Co_, (unsigned short*)C16, K, N, base_epi, aux, tiles_n, (int)nstreams, blocks, nunits);
+        LBX_LAUNCH_OK();
+        return LIDBOX_OK;
     }
-    const Rows16Plan pl = plan_rows16(M, N, K, ws ? ws_bytes : 0, BKS);
+    g16_last_variant[0] = g16_last_variant[1] = g16_last_variant[2] = 0;
+    if (d.kernel == LIDBOX_K16S_DMA || d.kernel == LIDBOX_K16S_PP) {
+        const Dma16Choice& dc = d.dc;
+        g16_last_variant[0] = dc.bm; g16_last_variant[1] = dc.bn; g16_last_variant[2] = dc.stages;
+        record_plan16(d.kernel, dc.splits, dc.k_per_split, 0);
+        return launch_rows16s_dma(dc, Ah_, Bh_, Co_, (unsigned short*)C16, (float*)ws, M, K, N, epi, aux, mask16, st, rj);
+    }
+    const Rows16Plan pl = d.pl;
     const size_t lds_bytes = 4 * (size_t)TILE_S * sizeof(__bf16);
     static bool lds_attr_set = false;
     if (lds_bytes > 65536 && !lds_attr_set) {
@@ -1275,19 +1338,10 @@ int launch_rows16s(const char* fn, lidbox_rows_t A, const void* B16, long ldb, l
         }
         return LIDBOX_OK;
     };
-    const long slots = (long)WAVES_S * NUM_CU;
-    const long tiles = lbx_cdiv(M, BT) * tiles_n;
-    if (pl.splits == 1 && tiles > slots && K >= TAIL_MIN_K) {
-        const long rounds = tiles / slots, rem_tiles = tiles - rounds * slots;
-        const long main_tiles_m = rounds * slots / tiles_n;
-        const long m_main = main_tiles_m * BT, m_rem = M - m_main;
-        if (rounds >= TAIL_MIN_ROUNDS && rem_tiles > 0 && rem_tiles <= slots / 4 && main_tiles_m >= 1 && m_rem > 0) {
-            const Rows16Plan rp = plan_rows16(m_rem, N, K, ws ? ws_bytes : 0, BKS);
-            if (rp.splits > 1) {
-                if (int rc = launch_range(0, m_main, pl)) return rc;
-                return launch_range(m_main, M, rp);
-            }
-        }
+    record_plan16(LIDBOX_K16S_ROWS, pl.splits, pl.k_per_split, d.tail.m_main);
+    if (d.tail.m_main > 0) {
+        if (int rc = launch_range(0, d.tail.m_main, pl)) return rc;
+        return launch_range(d.tail.m_main, M, d.tail.rem);
     }
     return launch_range(0, M, pl);
 }
@@ -1312,7 +1366,8 @@ extern "C" int lidbox_gemm_bf16s_nt_carry(lidbox_rows_t A16, const void* B16, lo
         if (jobs[i].nblocks == 0) continue;
         LBX_ARG(m < MAX_CARRY, "at most 2 non-empty jobs per call");
         memcpy(&js[m], jobs + i, sizeof(ReduceJob));
-        LBX_ARG((const void*)js[m].P != workspace, "a job's slices live in this call's workspace");
+        // (a zero job has no slices: P == NULL must not be mistaken for a call without a workspace)
+        LBX_ARG(!js[m].P || (const void*)js[m].P != workspace, "a job's slices live in this call's workspace");
         LBX_ARG(js[m].splits >= 0, "an optimizer-prepare job runs through lidbox_reduce_jobs_run only");
         ++m;
     }
@@ -1402,7 +1457,7 @@ extern "C" int lidbox_gemm_bf16s_nt_pair_carry(lidbox_rows_t A0, const void* B0,
         if (jobs[i].nblocks == 0) continue;
         if (m >= MAX_CARRY) { jobs_ok = false; break; }
         memcpy(&js[m], jobs + i, sizeof(ReduceJob));
-        if ((const void*)js[m].P == workspace || js[m].splits < 0) { jobs_ok = false; break; }
+        if ((js[m].P && (const void*)js[m].P == workspace) || js[m].splits < 0) { jobs_ok = false; break; }
         ++m;
     }
     if (jobs_ok && getenv("LIDBOX_GEMM_NO_CARRY") == nullptr && aligned16(workspace) &&
@@ -1415,6 +1470,7 @@ extern "C" int lidbox_gemm_bf16s_nt_pair_carry(lidbox_rows_t A0, const void* B0,
         g16_last_pair = 1;
         g16_last_carried = m;
         g16_last_variant[0] = 256; g16_last_variant[1] = 256; g16_last_variant[2] = 2;
+        record_plan16(LIDBOX_K16S_PP, 1, 0, 0);
         return LIDBOX_OK;
     }
     int rc = lidbox_gemm_bf16s_nt_carry(A0, B0, ldb0, C0, C16_0, K0, N0, epilogue0, aux0, workspace, workspace_bytes, jobs, njobs, stream);
@@ -1433,6 +1489,66 @@ extern "C" int lidbox_gemm_bf16s_last_variant(int* out3) {
     out3[0] = g16_last_variant[0]; out3[1] = g16_last_variant[1]; out3[2] = g16_last_variant[2];
     return LIDBOX_OK;
 }
+
+namespace {
+// the alignment the storage wgrad needs (lidbox_gemm_bf16s_tn / _tn_partial)
+bool tn16s_operands_ok(const lidbox_rows_t& A16, const lidbox_rows_t& B16, int K1, int N, const void* workspace) {
+    auto ok16 = [](const lidbox_rows_t& r) {
+        return aligned16(r.base) && r.row_stride % 8 == 0 && (r.batch == 1 || r.batch_stride % 8 == 0);
+    };
+    // a row is read as whole 16-byte pieces: the last piece of a width that is not a multiple of 8 must still lie inside the
+    // row's stride (a shadow padded to 8-element rows); what it holds beyond the width only reaches outputs never stored
+    auto width_ok = [](const lidbox_rows_t& r, int w) { return w % 8 == 0 || r.row_stride >= (long)((w + 7) / 8) * 8; };
+    return ok16(A16) && ok16(B16) && width_ok(A16, K1) && width_ok(B16, N) && aligned16(workspace);
+}
+
+// Which kernel a storage wgrad runs and how its rows are sliced (lidbox_gemm_bf16s_tn_partial follows it;
+// lidbox_gemm_bf16_plan_query reports it).  ws_bytes: 0 without a workspace.
+struct Tn16sPlan {
+    int kernel;                         // LIDBOX_K16S_TN | _TN_PP | _TN_KRES
+    int splits;                         // slices
+    long rows_per_split;                // _TN_KRES: 0 (slices are ranges of `ups` utterances)
+    int ups;
+    bool ws_ok;                         // the workspace holds the slices
+};
+
+Tn16sPlan plan_tn16s(const lidbox_rows_t& A16, const lidbox_rows_t& B16, long M, int K1, int N, size_t ws_bytes) {
+    Tn16Plan pl = plan_tn16(M, K1, N, BKT);
+    TnPpPlan pp = plan_tn16_pp(M, K1, N);
+    // the ping-pong tile addresses a row as a 32-bit byte offset from the tile's first column and walks both operands with one
+    // (utterance, row) counter: same utterance length on both sides, everything within 4 GB of the base, whole 16-byte chunks
+    auto span_ok = [&](const lidbox_rows_t& r, int w) {
+        const double span = ((double)(r.batch - 1) * (double)r.batch_stride + (double)(r.rows_per_batch - 1) * (double)r.row_stride + w) * 2.0;
+        return r.batch_stride >= 0 && r.row_stride >= 0 && span < 4.0e9;
+    };
+    if (pp.use && !(span_ok(A16, K1) && span_ok(B16, N) && K1 % 8 == 0 && N % 8 == 0 &&
+                    ((A16.batch == 1 && B16.batch == 1) || (A16.batch == B16.batch && A16.rows_per_batch == B16.rows_per_batch))))
+        pp.use = false;
+    // the K1-resident kernel (gemm16_tn_kres.h): short contraction over overlapping windows, the whole K1 extent in one workgroup's
+    // accumulators.  It walks the input as one flattened sequence of rows: utterances a whole number of row strides apart, at least as
+    // many of those as output rows, one stage's frames inside its LDS image; same utterance structure on both operands.
+    const TnKresPlan kp = plan_tn16_kres(M, K1, N);
+    // (slices are ranges of utterances: with fewer utterances than half the slices the chip would be mostly idle)
+    const bool desc_ok = kp.shape_ok && (kp.forced || 2 * A16.batch >= kp.max_slices) && A16.batch == B16.batch &&
+                         A16.rows_per_batch == B16.rows_per_batch &&
+                         A16.row_stride > 0 && (A16.batch == 1 || A16.batch_stride % A16.row_stride == 0) &&
+                         (A16.batch == 1 || A16.batch_stride / A16.row_stride >= A16.rows_per_batch) &&
+                         63 * A16.row_stride + K1 <= TKR_IMG_ELEMS &&
+                         (63 + lbx_cdiv(K1, A16.row_stride)) * tkr_img_stride((int)A16.row_stride) <= TKR_IMG_BYTES && span_ok(A16, K1) &&
+                         span_ok(B16, N);
+    if (desc_ok) {
+        const int batch = A16.batch;
+        int slices = kp.max_slices < batch ? kp.max_slices : batch;
+        const int ups = (int)lbx_cdiv(batch, slices);
+        slices = (int)lbx_cdiv(batch, ups);
+        const size_t need_k = ((size_t)slices * K1 * N + (size_t)slices * N) * sizeof(float);
+        if (ws_bytes >= need_k) return Tn16sPlan{LIDBOX_K16S_TN_KRES, slices, 0, ups, true};
+    }
+    if (pp.use) pl = Tn16Plan{pp.splits, pp.rows_per_split};
+    const size_t need = ((size_t)pl.splits * K1 * N + (size_t)pl.splits * N) * sizeof(float);
+    return Tn16sPlan{pp.use ? LIDBOX_K16S_TN_PP : LIDBOX_K16S_TN, pl.splits, pl.rows_per_split, 0, ws_bytes >= need};
+}
+}  // namespace
 
 extern "C" size_t lidbox_gemm_bf16s_tn_workspace(int M, int K1, int N) {
     if (M <= 0 || K1 <= 0 || N <= 0) return 0;
@@ -1470,87 +1586,54 @@ extern "C" int lidbox_gemm_bf16s_tn_partial(lidbox_rows_t A16, lidbox_rows_t B16
     const long M = (long)A16.batch * A16.rows_per_batch;
     LBX_ARG(M == (long)B16.batch * B16.rows_per_batch, "A and B row counts differ");
     LBX_ARG(M >= 1, "M >= 1");
-    auto ok16 = [](const lidbox_rows_t& r) {
-        return aligned16(r.base) && r.row_stride % 8 == 0 && (r.batch == 1 || r.batch_stride % 8 == 0);
-    };
-    // a row is read as whole 16-byte pieces: the last piece of a width that is not a multiple of 8 must still lie inside the
-    // row's stride (a shadow padded to 8-element rows); what it holds beyond the width only reaches outputs never stored
-    auto width_ok = [](const lidbox_rows_t& r, int w) { return w % 8 == 0 || r.row_stride >= (long)((w + 7) / 8) * 8; };
-    LBX_ARG(ok16(A16) && ok16(B16) && width_ok(A16, K1) && width_ok(B16, N) && aligned16(workspace),
+    LBX_ARG(tn16s_operands_ok(A16, B16, K1, N, workspace),
             "bf16-storage operands need 16-byte aligned bases, row and batch strides (in bf16 elements) that are multiples of 8, and "
             "K1 / N that are multiples of 8 or rows padded to one");
-    Tn16Plan pl = plan_tn16(M, K1, N, BKT);
-    TnPpPlan pp = plan_tn16_pp(M, K1, N);
-    // the ping-pong tile addresses a row as a 32-bit byte offset from the tile's first column and walks both operands with one
-    // (utterance, row) counter: same utterance length on both sides, everything within 4 GB of the base, whole 16-byte chunks
-    auto span_ok = [&](const lidbox_rows_t& r, int w) {
-        const double span = ((double)(r.batch - 1) * (double)r.batch_stride + (double)(r.rows_per_batch - 1) * (double)r.row_stride + w) * 2.0;
-        return r.batch_stride >= 0 && r.row_stride >= 0 && span < 4.0e9;
-    };
-    if (pp.use && !(span_ok(A16, K1) && span_ok(B16, N) && K1 % 8 == 0 && N % 8 == 0 &&
-                    ((A16.batch == 1 && B16.batch == 1) || (A16.batch == B16.batch && A16.rows_per_batch == B16.rows_per_batch))))
-        pp.use = false;
+    const Tn16sPlan d = plan_tn16s(A16, B16, M, K1, N, workspace ? workspace_bytes : 0);
     hipStream_t st = (hipStream_t)stream;
-    // the K1-resident kernel (gemm16_tn_kres.h): short contraction over overlapping windows, the whole K1 extent in one workgroup's
-    // accumulators.  It walks the input as one flattened sequence of rows: utterances a whole number of row strides apart, at least as
-    // many of those as output rows, one stage's frames inside its LDS image; same utterance structure on both operands.
     g16_tn_last_kres = 0;
-    {
-        const TnKresPlan kp = plan_tn16_kres(M, K1, N);
-        // (slices are ranges of utterances: with fewer utterances than half the slices the chip would be mostly idle)
-        const bool desc_ok = kp.shape_ok && (kp.forced || 2 * A16.batch >= kp.max_slices) && A16.batch == B16.batch &&
-                             A16.rows_per_batch == B16.rows_per_batch &&
-                             A16.row_stride > 0 && (A16.batch == 1 || A16.batch_stride % A16.row_stride == 0) &&
-                             (A16.batch == 1 || A16.batch_stride / A16.row_stride >= A16.rows_per_batch) &&
-                             63 * A16.row_stride + K1 <= TKR_IMG_ELEMS &&
-                             (63 + lbx_cdiv(K1, A16.row_stride)) * tkr_img_stride((int)A16.row_stride) <= TKR_IMG_BYTES && span_ok(A16, K1) &&
-                             span_ok(B16, N);
-        if (desc_ok) {
-            const int batch = A16.batch;
-            int slices = kp.max_slices < batch ? kp.max_slices : batch;
-            const int ups = (int)lbx_cdiv(batch, slices);
-            slices = (int)lbx_cdiv(batch, ups);
-            const size_t need_k = ((size_t)slices * K1 * N + (size_t)slices * N) * sizeof(float);
-            if (workspace && workspace_bytes >= need_k) {
-                const int tiles_n = N / TKR_BN;
-                const int Tq = batch == 1 ? A16.rows_per_batch : (int)(A16.batch_stride / A16.row_stride);
-                const long a_elems = (long)(batch - 1) * A16.batch_stride + (long)(A16.rows_per_batch - 1) * A16.row_stride + K1;
-                const long b_bytes = ((long)(batch - 1) * B16.batch_stride + (long)(B16.rows_per_batch - 1) * B16.row_stride + N) * 2;
-                float* P = (float*)workspace;
-                float* Pc = bias_grad ? P + (size_t)slices * K1 * N : nullptr;
-                const RowsH Ah{(const __bf16*)A16.base, A16.batch_stride, A16.row_stride, A16.batch, A16.rows_per_batch};
-                const RowsH Bh{(const __bf16*)B16.base, B16.batch_stride, B16.row_stride, B16.batch, B16.rows_per_batch};
-                {
-                    int dev = 0;
-                    LBX_HIP(hipGetDevice(&dev));
-                    static std::atomic<unsigned long long> attr_set{0};
-                    if (dev >= 64 || !((attr_set.load() >> dev) & 1ull)) {
-                        LBX_HIP(hipFuncSetAttribute((const void*)gemm16s_tn_kres_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TKR_LDS_BYTES));
-                        if (dev < 64) attr_set.fetch_or(1ull << dev);
-                    }
-                }
-                hipLaunchKernelGGL(gemm16s_tn_kres_kernel, dim3((unsigned)(tiles_n * slices)), dim3(512), TKR_LDS_BYTES, st, Ah, Bh, P, Pc, K1, N,
-                                   tiles_n, ups, Tq, a_elems, b_bytes);
-                LBX_LAUNCH_OK();
-                g16_tn_last_kres = slices;
-                g16_tn_last_pp = 0;
-                const long n = (long)K1 * N;
-                if (reduce_job_vec_ok(P, Pc, slices, n, N, Cm, ldc, bias_grad)) {
-                    const ReduceJob j = make_reduce_job(P, Pc, slices, n, N, Cm, ldc, accumulate, bias_grad);
-                    memcpy(job, &j, sizeof j);
-                    return LIDBOX_OK;
-                }
-                launch_splitk_reduce((const float*)P, (const float*)Pc, slices, n, N, Cm, ldc, accumulate, bias_grad, st);
-                LBX_LAUNCH_OK();
-                return LIDBOX_OK;
+    if (d.kernel == LIDBOX_K16S_TN_KRES) {
+        const int batch = A16.batch;
+        const int slices = d.splits, ups = d.ups;
+        const int tiles_n = N / TKR_BN;
+        const int Tq = batch == 1 ? A16.rows_per_batch : (int)(A16.batch_stride / A16.row_stride);
+        const long a_elems = (long)(batch - 1) * A16.batch_stride + (long)(A16.rows_per_batch - 1) * A16.row_stride + K1;
+        const long b_bytes = ((long)(batch - 1) * B16.batch_stride + (long)(B16.rows_per_batch - 1) * B16.row_stride + N) * 2;
+        float* P = (float*)workspace;
+        float* Pc = bias_grad ? P + (size_t)slices * K1 * N : nullptr;
+        const RowsH Ah{(const __bf16*)A16.base, A16.batch_stride, A16.row_stride, A16.batch, A16.rows_per_batch};
+        const RowsH Bh{(const __bf16*)B16.base, B16.batch_stride, B16.row_stride, B16.batch, B16.rows_per_batch};
+        {
+            int dev = 0;
+            LBX_HIP(hipGetDevice(&dev));
+            static std::atomic<unsigned long long> attr_set{0};
+            if (dev >= 64 || !((attr_set.load() >> dev) & 1ull)) {
+                LBX_HIP(hipFuncSetAttribute((const void*)gemm16s_tn_kres_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TKR_LDS_BYTES));
+                if (dev < 64) attr_set.fetch_or(1ull << dev);
             }
         }
+        hipLaunchKernelGGL(gemm16s_tn_kres_kernel, dim3((unsigned)(tiles_n * slices)), dim3(512), TKR_LDS_BYTES, st, Ah, Bh, P, Pc, K1, N,
+                           tiles_n, ups, Tq, a_elems, b_bytes);
+        LBX_LAUNCH_OK();
+        g16_tn_last_kres = slices;
+        g16_tn_last_pp = 0;
+        record_plan16(d.kernel, slices, ups, 0);
+        const long n = (long)K1 * N;
+        if (reduce_job_vec_ok(P, Pc, slices, n, N, Cm, ldc, bias_grad)) {
+            const ReduceJob j = make_reduce_job(P, Pc, slices, n, N, Cm, ldc, accumulate, bias_grad);
+            memcpy(job, &j, sizeof j);
+            return LIDBOX_OK;
+        }
+        launch_splitk_reduce((const float*)P, (const float*)Pc, slices, n, N, Cm, ldc, accumulate, bias_grad, st);
+        LBX_LAUNCH_OK();
+        return LIDBOX_OK;
     }
-    if (pp.use) pl = Tn16Plan{pp.splits, pp.rows_per_split};
-    g16_tn_last_pp = pp.use ? pp.splits : 0;
-    const size_t need = ((size_t)pl.splits * K1 * N + (size_t)pl.splits * N) * sizeof(float);
-    LBX_ARG(workspace && workspace_bytes >= need, "workspace too small (lidbox_gemm_bf16s_tn_workspace)");
-    if (pp.use) {
+    const Tn16Plan pl{d.splits, d.rows_per_split};
+    const bool use_pp = d.kernel == LIDBOX_K16S_TN_PP;
+    g16_tn_last_pp = use_pp ? pl.splits : 0;
+    LBX_ARG(d.ws_ok, "workspace too small (lidbox_gemm_bf16s_tn_workspace)");
+    record_plan16(d.kernel, pl.splits, pl.rows_per_split, 0);
+    if (use_pp) {
         int dev = 0;
         LBX_HIP(hipGetDevice(&dev));
         static std::atomic<unsigned long long> attr_set{0};
@@ -1702,6 +1785,13 @@ extern "C" int lidbox_gemm_bf16_nt(lidbox_rows_t A, const float* Bm, long ldb, l
                                (hipStream_t)stream);
 }
 
+namespace {
+// the alignment the fp32-source wgrad needs (lidbox_gemm_bf16_tn)
+bool tn16_operands_ok(const lidbox_rows_t& A, const lidbox_rows_t& Bd, int K1, int N, const void* workspace) {
+    return rows_aligned(A) && rows_aligned(Bd) && K1 % 4 == 0 && N % 4 == 0 && aligned16(workspace);
+}
+}  // namespace
+
 extern "C" size_t lidbox_gemm_bf16_tn_workspace(int M, int K1, int N) {
     if (M <= 0 || K1 <= 0 || N <= 0) return 0;
     const Tn16Plan pl = plan_tn16(M, K1, N);
@@ -1717,10 +1807,11 @@ extern "C" int lidbox_gemm_bf16_tn(lidbox_rows_t A, lidbox_rows_t Bd, float* Cm,
     const long M = (long)A.batch * A.rows_per_batch;
     LBX_ARG(M == (long)Bd.batch * Bd.rows_per_batch, "A and B row counts differ");
     LBX_ARG(M >= 1, "M >= 1");
-    LBX_ARG(rows_aligned(A) && rows_aligned(Bd) && K1 % 4 == 0 && N % 4 == 0 && aligned16(workspace), ALIGN_MSG);
+    LBX_ARG(tn16_operands_ok(A, Bd, K1, N, workspace), ALIGN_MSG);
     const Tn16Plan pl = plan_tn16(M, K1, N);
     const size_t need = ((size_t)pl.splits * K1 * N + (size_t)pl.splits * N) * sizeof(float);
     LBX_ARG(workspace && workspace_bytes >= need, "workspace too small (lidbox_gemm_bf16_tn_workspace)");
+    record_plan16(LIDBOX_K16_TN, pl.splits, pl.rows_per_split, 0);
     hipStream_t st = (hipStream_t)stream;
     const int tiles_n = (int)lbx_cdiv(N, BT);
     const int ntiles = (int)(lbx_cdiv(K1, BT) * tiles_n);
@@ -1732,5 +1823,70 @@ extern "C" int lidbox_gemm_bf16_tn(lidbox_rows_t A, lidbox_rows_t Bd, float* Cm,
     const long n = (long)K1 * N;
     launch_splitk_reduce((const float*)P, (const float*)Pc, pl.splits, n, N, Cm, ldc, accumulate, bias_grad, st);
     LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+// ---- the planner as a query: launches nothing, needs no device (tests, profiling tools)
+extern "C" int lidbox_gemm_bf16_last_plan(long* out4) {
+    LBX_ARG(out4, "out4 != NULL");
+    for (int i = 0; i < 4; ++i) out4[i] = g16_last_plan[i];
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_gemm_bf16_plan_query(int kind, lidbox_rows_t A, lidbox_rows_t B, lidbox_rows_out_t C, const void* C16, int K, int N,
+                                           int epilogue, const void* aux, int njobs, const void* workspace, size_t workspace_bytes,
+                                           long* out12) {
+    LBX_ARG(out12, "out12 != NULL");
+    LBX_ARG(kind >= LIDBOX_Q16_NN && kind <= LIDBOX_Q16S_TN, "kind is one of LIDBOX_Q16_*");
+    for (int i = 0; i < 12; ++i) out12[i] = 0;
+    const long M = (long)A.batch * A.rows_per_batch;
+    const size_t wsb = workspace ? workspace_bytes : 0;
+    if (kind == LIDBOX_Q16_NN || kind == LIDBOX_Q16_NT) {
+        if (M == 0 || N == 0) return LIDBOX_OK;
+        if (!rows16_operands_ok(kind == LIDBOX_Q16_NT, A, B.base, B.row_stride, C, K, N, workspace)) { out12[0] = LIDBOX_K16_REFUSED; return LIDBOX_OK; }
+        const Rows16Plan pl = plan_rows16(M, N, K, wsb);
+        const Rows16Tail t = plan_tail16(pl, M, N, K, wsb, 32, 2 * NUM_CU);
+        out12[0] = LIDBOX_K16_ROWS; out12[4] = pl.splits; out12[5] = pl.k_per_split; out12[6] = t.m_main;
+        if (t.m_main > 0) { out12[7] = t.rem.splits; out12[8] = t.rem.k_per_split; }
+        out12[9] = (pl.splits > 1 || t.m_main > 0) ? LIDBOX_R16_ROWS : LIDBOX_R16_NONE;
+        return LIDBOX_OK;
+    }
+    if (kind == LIDBOX_Q16S_NT) {
+        if (M == 0 || N == 0) return LIDBOX_OK;
+        if (!rows16s_operands_ok(A, B.base, B.row_stride, C, C16, K, workspace)) { out12[0] = LIDBOX_K16_REFUSED; return LIDBOX_OK; }
+        const bool mask16 = (epilogue & LIDBOX_EPI_MASK_BF16) != 0;
+        const bool carries = njobs > 0 && getenv("LIDBOX_GEMM_NO_CARRY") == nullptr;
+        const Rows16sPlan d = plan_rows16s(A, B.row_stride, C, C16, K, N, epilogue & ~LIDBOX_EPI_MASK_BF16, mask16, carries, wsb);
+        out12[0] = d.kernel;
+        if (d.kernel == LIDBOX_K16S_KRES13 || d.kernel == LIDBOX_K16S_KRES0) {
+            out12[1] = 1; out12[2] = KRES_BN; out12[3] = 1; out12[4] = 1; out12[5] = K;
+        } else if (d.kernel == LIDBOX_K16S_ROWS) {
+            out12[4] = d.pl.splits; out12[5] = d.pl.k_per_split; out12[6] = d.tail.m_main;
+            if (d.tail.m_main > 0) { out12[7] = d.tail.rem.splits; out12[8] = d.tail.rem.k_per_split; }
+            out12[9] = (d.pl.splits > 1 || d.tail.m_main > 0) ? LIDBOX_R16_ROWS : LIDBOX_R16_NONE;
+        } else {
+            out12[1] = d.dc.bm; out12[2] = d.dc.bn; out12[3] = d.dc.stages; out12[4] = d.dc.splits; out12[5] = d.dc.k_per_split;
+            out12[9] = d.dc.splits > 1 ? LIDBOX_R16_ROWS : LIDBOX_R16_NONE;
+        }
+        return LIDBOX_OK;
+    }
+    // wgrads: C.base = the output, C.row_stride = ldc, aux = bias_grad
+    if (M < 1 || M != (long)B.batch * B.rows_per_batch || K < 1 || N < 1 || C.row_stride < N) { out12[0] = LIDBOX_K16_REFUSED; return LIDBOX_OK; }
+    int splits;
+    if (kind == LIDBOX_Q16_TN) {
+        if (!tn16_operands_ok(A, B, K, N, workspace)) { out12[0] = LIDBOX_K16_REFUSED; return LIDBOX_OK; }
+        const Tn16Plan pl = plan_tn16(M, K, N);
+        splits = pl.splits;
+        out12[0] = LIDBOX_K16_TN; out12[4] = pl.splits; out12[5] = pl.rows_per_split;
+        out12[10] = wsb >= ((size_t)pl.splits * K * N + (size_t)pl.splits * N) * sizeof(float);
+    } else {
+        if (!tn16s_operands_ok(A, B, K, N, workspace)) { out12[0] = LIDBOX_K16_REFUSED; return LIDBOX_OK; }
+        const Tn16sPlan d = plan_tn16s(A, B, M, K, N, wsb);
+        splits = d.splits;
+        out12[0] = d.kernel; out12[4] = d.splits; out12[5] = d.rows_per_split; out12[10] = d.ws_ok; out12[11] = d.ups;
+    }
+    const float* P = (const float*)workspace;
+    const float* Pc = aux ? P + (size_t)splits * K * N : nullptr;
+    out12[9] = reduce_job_vec_ok(P, Pc, splits, (long)K * N, N, C.base, C.row_stride, (const float*)aux) ? LIDBOX_R16_JOB4 : LIDBOX_R16_SCALAR;
     return LIDBOX_OK;
 }

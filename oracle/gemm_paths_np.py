@@ -38,8 +38,8 @@ numpy only; tests/test_oracle_gemm_paths.py checks every restated function again
 Largest err / bound seen on the device (one run on one MI355X; the figures per kernel stand in the docstring of
 tests/test_gemm_paths_gpu.py): 0.21 (gemm_rows_kernel, K = 36 .. 52); every `exact` case bit-equal.
 
-Out of scope here: the 32-bit-extent refusals (sk_extent_ok, sk_b_extent_ok need allocations above 4 GB); the bf16 family
-(gemm_bf16.hip, gemm16_*.h).
+Out of scope here: the 32-bit-extent refusals (sk_extent_ok, sk_b_extent_ok need allocations above 4 GB).  The bf16 families
+(gemm_bf16.hip, gemm16_*.h) have their own module, oracle/gemm16_paths_np.py, which imports this one's helpers.
 lidbox_gemm_nt_tn_carry with pending jobs stays with tests/test_gemm_sk_gpu.py (bit identity).
 """
 import os
