@@ -889,6 +889,36 @@ int lidbox_gru_fwd(const float* U0, const float* U1, const float* b_rec0, const 
 int lidbox_gru_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* hseq, float* qh,
                    const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
                    lidbox_stream_t stream);
+/* ------------------------------------------------------------------ ragged recurrence, forward only (csrc/rnn_ragged.hip)
+ * lidbox_lstm_step_fwd / lidbox_gru_fwd for B utterances of DIFFERENT lengths T_b >= 1 in one walk of max T_b steps (inference;
+ * no reference counterpart: the Keras layers run without masking, so a padded batch is a different computation).  The dense
+ * [B][T+2] convention with a per-utterance T: utterance b owns the rows seg[b] .. seg[b+1] = seg[b] + T_b + 2 of every
+ * per-frame buffer, frame t at row seg[b] + 1 + t, the first and last row of a segment are pad rows; lidbox_ragged_pack_rows
+ * with pad = 1 and seg_offsets = seg makes this layout from [total_T, C] frames.
+ *   rows    rows per direction of zg and cseq / qh, >= sum of T_b + 2 B
+ *   zg      [dirs][rows][4H | 3H]: X W_d + b_d on entry (one GEMM over all rows; pad rows are neither read nor written),
+ *           the gates on return, as the dense calls leave them
+ *   cseq | qh [dirs][rows][H];  hseq [rows][h_row_stride] (GRU: [rows][dirs*H]): h_t of direction d at the frame's row,
+ *           columns d*H.. of the pointer passed; pad rows are neither read nor written
+ *   hlast   (may be NULL) [B][dirs*H] in the caller's utterance order: each direction's final h (t = T_b-1 forward, 0 reverse)
+ *   slots   device [3][B]: slot j = the j-th longest utterance under a stable sort by length, descending: its first row
+ *           seg[b], its length T_b, its index b (read only when hlast != NULL).  The kernels trust this table.
+ *   sorted_lengths  HOST [B]: the lengths in slot order; >= 1 and non-increasing, or LIDBOX_E_INVALID.  Step s is one launch
+ *           over the n_s = #{b : T_b > s} leading slots, grid ceil(n_s / 64) x ceil(H / 16) x dirs.
+ * The k order of every output element and the cell code are those of the dense step kernels: every utterance's gates, c / qh,
+ * h and hlast are bit for bit what lidbox_lstm_step_fwd / lidbox_gru_fwd give it at B = 1, T = T_b, whatever its neighbours,
+ * place and slot; load paths as the dense calls.  No atomics, no communication between workgroups.  B = 0 is a no-op. */
+int lidbox_lstm_ragged_fwd(const float* U0, const float* U1, int dirs, int B, int H, long rows, const long* slots,
+                           const long* sorted_lengths, float* zg, float* hseq, long h_row_stride, float* cseq, float* hlast,
+                           lidbox_stream_t stream);
+int lidbox_gru_ragged_fwd(const float* U0, const float* U1, const float* b_rec0, const float* b_rec1, int dirs, int B, int H,
+                          long rows, const long* slots, const long* sorted_lengths, float* zg, float* hseq, float* qh,
+                          float* hlast, lidbox_stream_t stream);
+/* lidbox_seq_avg_pool_fwd per utterance: out[b, c] (ldo floats between rows) = alpha * mean of the lengths[b] >= 1 rows
+ * (row_stride floats apart) from row first_rows[b] of x; int64 device arrays.  Summation order of the ragged pools above
+ * (16 time groups in order, combined in order), so a result depends on neither the neighbours nor the place in the batch. */
+int lidbox_seq_avg_pool_ragged_fwd(const float* x, long row_stride, const long* first_rows, const long* lengths, long B, int C,
+                                   float alpha, float* out, long ldo, lidbox_stream_t stream);
 
 /* ------------------------------------------------------------------ Conv2D / MaxPool2D (lidbox/models/crnn.py:36-41)
  * tf.keras.layers.Conv2D(C_out, k, padding="same") with stride 1 and an odd k, on images stored time-major: x [B][T][F][C_in]

@@ -217,6 +217,9 @@ _SIGS = {
     "lidbox_gru_workspace": (_sz, [_i, _i, _i, _i]),
     "lidbox_gru_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lidbox_gru_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "lidbox_lstm_ragged_fwd": (_i, [_vp, _vp, _i, _i, _i, _l, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp]),
+    "lidbox_gru_ragged_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lidbox_seq_avg_pool_ragged_fwd": (_i, [_vp, _l, _vp, _vp, _l, _i, _f, _vp, _l, _vp]),
     "lidbox_conv2d_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "lidbox_conv2d_dgrad_workspace": (_sz, [_i, _i, _i]),
     "lidbox_conv2d_dgrad": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),

@@ -36,6 +36,10 @@ class EmbeddingExtractor:
 
     predict = __call__
 
+    def ragged(self, X, row_offsets):
+        """the embeddings [B, num_fc_units] of B utterances of different lengths (GRUModel.embed_ragged)"""
+        return self.model.embed_ragged(X, row_offsets)
+
 
 def as_embedding_extractor(model):
     return EmbeddingExtractor(model)

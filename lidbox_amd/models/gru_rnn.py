@@ -26,6 +26,7 @@ import torch
 
 from .. import _native as nv
 from .flat import BatchNormSpec, FlatModel, Workspace, _rows, h_neighbour_rows
+from .rnn_ragged import RaggedRecurrent
 from .tdnn import DenseSpec
 
 
@@ -103,7 +104,7 @@ class _Workspace(Workspace):
         self.pending = []
 
 
-class GRUModel(FlatModel):
+class GRUModel(FlatModel, RaggedRecurrent):
     """[SpatialDropout1D] -> GRU layers -> final state -> [BatchNormalization] -> Dense [+ BatchNormalization] layers (see the
     module docstring)."""
 
@@ -184,6 +185,13 @@ class GRUModel(FlatModel):
             nv.check(lib.lidbox_gru_fwd(U0, U1, self._b_rec(l.prefixes[0]), self._b_rec(l.prefixes[-1]), l.dirs, B, T, l.units,
                                         nv.ptr(ws.zg[i]), nv.ptr(ws.hseq[i]), nv.ptr(ws.qh[i]),
                                         nv.ptr(ws.hlast) if last else None, st))
+        return self._forward_head(ws, training, update_moving, stop_before_output, embedding)
+
+    def _forward_head(self, ws, training=False, update_moving=True, stop_before_output=False, embedding=False):
+        """[BatchNormalization] -> Dense [+ BatchNormalization] layers -> output activation on the ws.B final states in
+        ws.hlast (the dense and the ragged pass share it); the return value is forward_ws's"""
+        st, lib, B = nv.current_stream(), nv.lib, ws.B
+        gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
         if self.rnn_bn is not None:
             self._bn_fwd(self.rnn_bn, ws.hlast, B, ws.hlast.shape[1], ws.c0, ws.y0, ws, training, update_moving)
         for j, (d, bn) in enumerate(zip(self.denses, self.dense_bns)):
@@ -264,6 +272,49 @@ class GRUModel(FlatModel):
                     dprev = ws.dseq[i - 1]
                     nv.check(lib.lidbox_gemm_nt(dzx, self._p(p + ".W"), H3, _rows(dprev.data_ptr(), 0, K, 1, B * T), H3, K,
                                                 nv.EPI_ACCUM if d > 0 else nv.EPI_NONE, None, gws, gws_n, st))
+
+    # ------------------------------------------------------------------ ragged pass (inference, float32; models/rnn_ragged.py)
+    def _ragged_embedding_dim(self):
+        return self.denses[0].units
+
+    def _ragged_buffers_rows(self, cap):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        H, dirs = max(l.units for l in self.grus), max(l.dirs for l in self.grus)
+        return dict(x=torch.zeros((cap, self.input_dim), **f32), zg=torch.zeros(dirs * cap * 3 * H, **f32),
+                    qh=torch.zeros(dirs * cap * H, **f32), hseq=[torch.zeros((cap, l.out_dim), **f32) for l in self.grus])
+
+    def _ragged_buffers_utts(self, cap):
+        """what _forward_head reads of a workspace, for `cap` utterances"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        D = self.grus[-1].out_dim
+        bufs = dict(hlast=torch.zeros((cap, D), **f32), h=[torch.zeros((cap, d.units), **f32) for d in self.denses],
+                    y=[torch.zeros((cap, d.units), **f32) if bn is not None else None for d, bn in zip(self.denses, self.dense_bns)],
+                    c=[torch.zeros((4, d.units), **f32) if bn is not None else None for d, bn in zip(self.denses, self.dense_bns)],
+                    emb=torch.zeros((cap, self.denses[0].units), **f32), logp=torch.zeros((cap, self.output_dim), **f32))
+        if self.rnn_bn is not None:
+            bufs.update(y0=torch.zeros((cap, D), **f32), c0=torch.zeros((4, D), **f32))
+        return bufs
+
+    def _forward_ragged(self, ws, plan, dev, upto_embedding):
+        """every GRU layer on the ragged walk (lidbox_gru_ragged_fwd), then the last layer's final states -- forward at every
+        utterance's own last frame, backward at its first -- through the head with the moving statistics"""
+        st, lib, B, Rp = nv.current_stream(), nv.lib, plan.B, plan.Rp
+        X, K = _rows(ws.x.data_ptr(), 0, self.input_dim, 1, Rp), self.input_dim
+        for i, l in enumerate(self.grus):
+            hs = ws.hseq[i]
+            hs[:Rp].zero_()                                   # the pad rows: the next layer's projection reads every row
+            self._ragged_projection(ws, plan, X, K, l.prefixes, 3 * l.units, ws.zg)
+            U0, U1 = self._U(l)
+            last = i == len(self.grus) - 1
+            nv.check(lib.lidbox_gru_ragged_fwd(U0, U1, self._b_rec(l.prefixes[0]), self._b_rec(l.prefixes[-1]), l.dirs, B, l.units,
+                                               Rp, dev.slots, dev.sorted_lengths, nv.ptr(ws.zg), nv.ptr(hs), nv.ptr(ws.qh),
+                                               nv.ptr(ws.hlast) if last else None, st))
+            X, K = _rows(hs.data_ptr(), 0, l.out_dim, 1, Rp), l.out_dim
+        need, din = 16, self.grus[-1].out_dim
+        for d in self.denses:
+            need, din = max(need, lib.lidbox_gemm_rows_workspace(B, d.units, din)), d.units
+        ws.reserve_gemm_ws(self, need)
+        return self._forward_head(ws, embedding=upto_embedding)
 
     # ------------------------------------------------------------------ public call
     def embed(self, x):

@@ -21,6 +21,12 @@ and row stride s_i C_i over level i lines every utterance's causal windows up wi
 so conv i is one GEMM over M_{i+1} - p_{i+1} rows.  It also writes the p_{i+1} pad rows of utterances 1 .. B-1 (zeroed again right
 behind the GEMM) and the slack rows, which no valid output row ever reads: the last frame's window ends at padded position
 (T_{i+1,b} - 1) s_i + k_i - 1 <= p_i + T_{i,b} - 1.  The last GEMM rows read up to k_i - 1 rows behind M_i, which the buffers have.
+
+`recurrent_plan` is the plan of the ragged RECURRENT pass (csrc/rnn_ragged.hip): the dense [B][T + 2] convention of the recurrence
+kernels with a per-utterance T.  Utterance b owns the rows seg[b] .. seg[b + 1] of every per-frame buffer of a layer, seg[b] =
+row_offsets[b] + 2 b: a pad row, its T_b frames, a pad row; Rp = total_T + 2 B rows in all.  The walk through time runs step s over
+the n_s = #{b : T_b > s} utterances that are still running; slot j of a step is the j-th longest utterance under a stable sort by
+length, descending, so the running ones are always the leading slots.
 """
 import numpy as np
 
@@ -62,3 +68,32 @@ def ragged_plan(lengths, convs):
         L = np.maximum(L, -(-(pads[i] + T[i]) // cum[i]))
     off = np.concatenate(([0], np.cumsum(L))).astype(np.int64)
     return RaggedPlan(pads, cum, T, L, off)
+
+
+class RecurrentPlan:
+    """seg [B + 1] (first row of every segment, Rp as entry B), order [B] (the utterance of slot j), sorted_lengths [B] (its
+    length: non-increasing), n_s [T_max] (utterances running at step s) -- int64 arrays -- and Rp"""
+
+    def __init__(self, lengths, seg, order, sorted_lengths, n_s):
+        self.lengths, self.seg, self.order, self.sorted_lengths, self.n_s = lengths, seg, order, sorted_lengths, n_s
+        self.B = len(lengths)
+        self.Rp = int(seg[-1])
+
+    def slots(self):
+        """the device table of the walk, [3, B]: per slot the utterance's first row, its length and its index"""
+        return np.ascontiguousarray(np.stack([self.seg[:-1][self.order], self.sorted_lengths, self.order]))
+
+
+def recurrent_plan(lengths):
+    """lengths: frames per utterance (each >= 1, ValueError otherwise).  Returns a RecurrentPlan."""
+    T = np.asarray(lengths, np.int64).reshape(-1)
+    if (T < 1).any():
+        raise ValueError("every utterance needs at least one frame, got lengths %s" % T[T < 1][:8].tolist())
+    B = len(T)
+    seg = np.concatenate(([0], np.cumsum(T))).astype(np.int64) + 2 * np.arange(B + 1, dtype=np.int64)
+    order = np.argsort(-T, kind="stable").astype(np.int64)
+    sorted_lengths = np.ascontiguousarray(T[order])
+    T_max = int(sorted_lengths[0]) if B else 0
+    # n_s = #{b : T_b > s}: the sorted lengths are non-increasing, so count from the short end
+    n_s = B - np.searchsorted(sorted_lengths[::-1], np.arange(T_max, dtype=np.int64), side="right").astype(np.int64)
+    return RecurrentPlan(T, seg, order, sorted_lengths, n_s)

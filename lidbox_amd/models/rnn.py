@@ -18,6 +18,7 @@ import torch
 
 from .. import _native as nv
 from .flat import FlatModel, LSTMLayer, Workspace, _rows, lstm_layer_bwd, lstm_layer_fwd, orthogonal
+from .rnn_ragged import RaggedRecurrent
 from .tdnn import DenseSpec
 
 
@@ -84,7 +85,7 @@ class _Workspace(Workspace):
         self.pending = []
 
 
-class RecurrentModel(FlatModel):
+class RecurrentModel(FlatModel, RaggedRecurrent):
     """[SpatialDropout1D] -> LSTM layers -> head, parameters in one flat buffer (see the module docstring)."""
 
     workspace_class = _Workspace
@@ -149,7 +150,6 @@ class RecurrentModel(FlatModel):
         st = nv.current_stream()
         lib = nv.lib
         B, T = ws.B, ws.T
-        gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
         for i in range(len(self.lstms)):
             lstm_layer_fwd(self, self._layer(ws, i))
         if self.head == "avg_concat":
@@ -164,7 +164,14 @@ class RecurrentModel(FlatModel):
                 nv.check(lib.lidbox_l2_normalize_fwd(nv.ptr(out), B, self.output_dim, nv.ptr(ws.out), st))
                 return ws.out
             return out
-        x, din = self._last_rows(ws), self.lstms[-1].out_dim
+        return self._forward_dense_head(ws, self._last_rows(ws), stop_before_output)
+
+    def _forward_dense_head(self, ws, x, stop_before_output=False):
+        """the Dense layers and the output activation of a 'last' head on x, the rows descriptor of the ws.B final states (the
+        dense and the ragged pass share it)"""
+        st, lib, B = nv.current_stream(), nv.lib, ws.B
+        gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
+        din = self.lstms[-1].out_dim
         for j, d in enumerate(self.denses):
             if stop_before_output and j == len(self.denses) - 1:
                 return x
@@ -173,6 +180,55 @@ class RecurrentModel(FlatModel):
                                         gws, gws_n, st))
             x, din = _rows(ws.h[j].data_ptr(), 0, d.units, 1, B), d.units
         return self._output_activation(ws, ws.h[-1], din)
+
+    # ------------------------------------------------------------------ ragged pass (inference, float32; models/rnn_ragged.py)
+    def _ragged_embedding_dim(self):
+        """'last': the final h, the output layer's input; 'avg_concat': the language vector, which is the model output"""
+        return self.lstms[-1].out_dim if self.head == "last" else self.output_dim
+
+    def _ragged_buffers_rows(self, cap):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        H, dirs = max(l.units for l in self.lstms), max(l.dirs for l in self.lstms)
+        return dict(x=torch.zeros((cap, self.input_dim), **f32), zg=torch.zeros(dirs * cap * 4 * H, **f32),
+                    cseq=torch.zeros(dirs * cap * H, **f32), hseq=[torch.zeros((cap, l.out_dim), **f32) for l in self.lstms])
+
+    def _ragged_buffers_utts(self, cap):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if self.head == "avg_concat":
+            h = [torch.zeros((cap, self.output_dim), **f32)]
+        else:
+            h = [torch.zeros((cap, d.units), **f32) for d in self.denses]
+        return dict(hlast=torch.zeros((cap, self.lstms[-1].out_dim), **f32), h=h, logp=torch.zeros_like(h[-1]),
+                    out=torch.zeros_like(h[-1]))
+
+    def _forward_ragged(self, ws, plan, dev, upto_embedding):
+        """every LSTM layer on the ragged walk (lidbox_lstm_ragged_fwd, whatever H), then the head: the final h of every
+        utterance into the Dense layers, or the alpha-scaled time averages over each utterance's own frames, L2-normalised"""
+        st, lib, B, Rp = nv.current_stream(), nv.lib, plan.B, plan.Rp
+        X, K = _rows(ws.x.data_ptr(), 0, self.input_dim, 1, Rp), self.input_dim
+        for i, l in enumerate(self.lstms):
+            hs = ws.hseq[i]
+            hs[:Rp].zero_()                                   # the pad rows: the next layer's projection reads every row
+            last = self.head == "last" and i == len(self.lstms) - 1
+            self._ragged_lstm_layer(ws, plan, dev, X, K, l.prefixes, l.units, hs.data_ptr(), l.out_dim, ws.hlast if last else None)
+            X, K = _rows(hs.data_ptr(), 0, l.out_dim, 1, Rp), l.out_dim
+        if self.head == "avg_concat":
+            out, col = ws.h[-1], 0
+            for i, l in enumerate(self.lstms):
+                nv.check(lib.lidbox_seq_avg_pool_ragged_fwd(nv.ptr(ws.hseq[i]), l.out_dim, dev.first, dev.lengths, B, l.out_dim,
+                                                            self.alphas[i], ctypes.c_void_p(out.data_ptr() + 4 * col),
+                                                            self.output_dim, st))
+                col += l.out_dim
+            nv.check(lib.lidbox_l2_normalize_fwd(nv.ptr(out), B, self.output_dim, nv.ptr(ws.out), st))
+            return ws.out
+        if upto_embedding:
+            return ws.hlast
+        need = 16
+        din = self.lstms[-1].out_dim
+        for d in self.denses:
+            need, din = max(need, lib.lidbox_gemm_rows_workspace(B, d.units, din)), d.units
+        ws.reserve_gemm_ws(self, need)
+        return self._forward_dense_head(ws, _rows(ws.hlast.data_ptr(), 0, self.lstms[-1].out_dim, 1, B))
 
     # ------------------------------------------------------------------ backward
     def backward_head_ws(self, ws):

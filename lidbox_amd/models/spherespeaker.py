@@ -27,6 +27,7 @@ import torch
 from .. import _native as nv
 from .flat import FlatModel, LSTMLayer, Workspace, _rows, lstm_layer_bwd, lstm_layer_fwd
 from .gru_rnn import BatchNormSpec
+from .rnn_ragged import RaggedRecurrent
 from .tdnn import DenseSpec
 
 NUM_BLSTM = 3
@@ -80,7 +81,7 @@ class _Workspace(Workspace):
         self.pending = []
 
 
-class SphereSpeakerModel(FlatModel):
+class SphereSpeakerModel(FlatModel, RaggedRecurrent):
     """Three stacked BLSTMs -> concat -> BatchNormalization -> Dense(relu) -> time average -> BatchNormalization -> L2
     normalisation -> Dense (see the module docstring)."""
 
@@ -146,7 +147,7 @@ class SphereSpeakerModel(FlatModel):
         st = nv.current_stream()
         lib = nv.lib
         B, T = ws.B, ws.T
-        E, N, C6 = self.embedding_dim, self.output_dim, self.concat_dim
+        E, C6 = self.embedding_dim, self.concat_dim
         R = B * T
         gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
         if B == 0:
@@ -161,14 +162,61 @@ class SphereSpeakerModel(FlatModel):
                                     _rows(ws.a.data_ptr(), 0, E, 1, R), C6, E, nv.EPI_BIAS_RELU, self._p("fc_relu.b"),
                                     gws, gws_n, st))
         nv.check(lib.lidbox_avg_pool_fwd(nv.ptr(ws.a), B, T, E, T * E, E, nv.ptr(ws.pooled), st))
+        return self._forward_pooled(ws, training, update_moving, embedding or stop_before_output)
+
+    def _forward_pooled(self, ws, training=False, update_moving=True, embedding=False):
+        """`pool_bn` -> L2 normalisation -> `outputs` -> output activation on the ws.B rows of ws.pooled (the dense and the
+        ragged pass share it); embedding: the l2_normalize layer's output"""
+        st, lib, B = nv.current_stream(), nv.lib, ws.B
+        E, N = self.embedding_dim, self.output_dim
+        gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
         self._bn_fwd(self.pool_bn, ws.pooled, B, E, ws.c_pool, ws.ypool, ws, training, update_moving)
         nv.check(lib.lidbox_l2_normalize_fwd(nv.ptr(ws.ypool), B, E, nv.ptr(ws.emb), st))
-        if embedding or stop_before_output:
+        if embedding:
             return ws.emb
         nv.check(lib.lidbox_gemm_nn(_rows(ws.emb.data_ptr(), 0, E, 1, B), self._p("outputs.W"), N,
                                     _rows(ws.h[-1].data_ptr(), 0, N, 1, B), E, N, nv.EPI_BIAS, self._p("outputs.b"),
                                     gws, gws_n, st))
         return self._output_activation(ws, ws.h[-1], N)
+
+    # ------------------------------------------------------------------ ragged pass (inference, float32; models/rnn_ragged.py)
+    def _ragged_embedding_dim(self):
+        return self.embedding_dim
+
+    def _ragged_buffers_rows(self, cap):
+        """the per-row buffers for `cap` rows (one zg / cseq serves the three layers in turn) and the BatchNormalization constants"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        H, E, C6 = self.units, self.embedding_dim, self.concat_dim
+        return dict(x=torch.zeros((cap, self.input_dim), **f32), zg=torch.zeros(2 * cap * 4 * H, **f32),
+                    cseq=torch.zeros(2 * cap * H, **f32), hcat=torch.zeros((cap, C6), **f32), ycat=torch.zeros((cap, C6), **f32),
+                    a=torch.zeros((cap, E), **f32), c_cat=torch.zeros((4, C6), **f32), c_pool=torch.zeros((4, E), **f32))
+
+    def _ragged_buffers_utts(self, cap):
+        """what _forward_pooled reads of a workspace, for `cap` utterances"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        E, N = self.embedding_dim, self.output_dim
+        return dict(pooled=torch.zeros((cap, E), **f32), ypool=torch.zeros((cap, E), **f32), emb=torch.zeros((cap, E), **f32),
+                    h=[torch.zeros((cap, N), **f32)], logp=torch.zeros((cap, N), **f32))
+
+    def _forward_ragged(self, ws, plan, dev, upto_embedding):
+        """the three BLSTMs on the ragged walk into their column slices of hcat [Rp, 6H]; `blstm_bn` and `fc_relu` on all Rp
+        rows, in buffers of their own, so that hcat's pad rows stay zero (what they make of a pad row is never read); the
+        average over each utterance's own frames; then the shared tail"""
+        st, lib, B, Rp = nv.current_stream(), nv.lib, plan.B, plan.Rp
+        H, E, N, C6 = self.units, self.embedding_dim, self.output_dim, self.concat_dim
+        ws.hcat[:Rp].zero_()                                  # the pad rows: projections, blstm_bn and fc_relu read every row
+        X, K = _rows(ws.x.data_ptr(), 0, self.input_dim, 1, Rp), self.input_dim
+        for i, wrapper in enumerate(self.blstms):
+            h = ws.hcat.data_ptr() + 4 * 2 * H * i
+            self._ragged_lstm_layer(ws, plan, dev, X, K, self.prefixes(wrapper), H, h, C6)
+            X, K = _rows(h, 0, C6, 1, Rp), 2 * H
+        ws.reserve_gemm_ws(self, max(16, lib.lidbox_gemm_rows_workspace(Rp, E, C6), lib.lidbox_gemm_rows_workspace(B, N, E)))
+        self._bn_fwd(self.cat_bn, ws.hcat, Rp, C6, ws.c_cat, ws.ycat, ws, False, False)
+        nv.check(lib.lidbox_gemm_nn(_rows(ws.ycat.data_ptr(), 0, C6, 1, Rp), self._p("fc_relu.W"), E,
+                                    _rows(ws.a.data_ptr(), 0, E, 1, Rp), C6, E, nv.EPI_BIAS_RELU, self._p("fc_relu.b"),
+                                    nv.ptr(ws.gemm_ws), ws.gemm_ws.numel(), st))
+        nv.check(lib.lidbox_avg_pool_ragged_fwd(nv.ptr(ws.a), E, dev.first, dev.lengths, B, E, nv.ptr(ws.pooled), st))
+        return self._forward_pooled(ws, embedding=upto_embedding)
 
     # ------------------------------------------------------------------ backward
 
@@ -240,6 +288,10 @@ class EmbeddingExtractor:
         return self.model.embed(x)
 
     predict = __call__
+
+    def ragged(self, X, row_offsets):
+        """the embeddings [B, embedding_dim] of B utterances of different lengths (SphereSpeakerModel.embed_ragged)"""
+        return self.model.embed_ragged(X, row_offsets)
 
 
 def as_embedding_extractor(model):
