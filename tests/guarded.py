@@ -1,6 +1,7 @@
 """
 The guarded device buffer of the dispatch-path modules (test_conv2d_paths_gpu.py, test_nnops_paths_gpu.py,
-test_bn_attention_paths_gpu.py, test_rnn_paths_gpu.py, test_gemm_paths_gpu.py, test_gemm16_paths_gpu.py): a payload inside a larger NaN-filled allocation whose words before and after the payload must
+test_bn_attention_paths_gpu.py, test_rnn_paths_gpu.py, test_gemm_paths_gpu.py, test_gemm16_paths_gpu.py,
+test_augment_paths_gpu.py): a payload inside a larger NaN-filled allocation whose words before and after the payload must
 still hold the fill afterwards.
 """
 import ctypes
