@@ -995,6 +995,32 @@ int lidbox_bn_relu_maxf_fwd(const float* x, int B, int T, int F, int C, const fl
                             long y_batch_stride, lidbox_stream_t stream);
 int lidbox_bn_relu_maxf_bwd(const float* x, int B, int T, int F, int C, const float* scale, const float* shift,
                             const float* dy, long dy_batch_stride, float* dx, lidbox_stream_t stream);
+/* ------------------------------------------------------------------ ragged Conv2D / MaxPool2D, forward only (csrc/conv2d.hip)
+ * The three forward calls above for B utterances of DIFFERENT lengths stored end to end (inference; no reference counterpart):
+ * images are [rows][F][C], utterance b owns the rows offsets[b] .. offsets[b + 1], with no gaps and no halo in storage.  All
+ * offsets are int64 device arrays of B + 1 entries rising from 0 (an entry may repeat: an empty utterance); the kernels trust
+ * them.  B == 0 or no rows: LIDBOX_OK without a launch.  NULL pointers, negative counts and C_out % 16 != 0 are refused with
+ * nothing written.  No atomics, no communication between workgroups: bit-identical from run to run.
+ *   lidbox_conv2d_ragged_fwd: lidbox_conv2d_fwd on x [total_T][F][C_in] -> y [total_T][F][C_out]; a tap whose time index falls
+ *     outside its own utterance contributes zero.  Tiles (128 pixels x 16 / 32 / 64 channels, laid over the concatenated pixels)
+ *     and the k-chain of every output are the dense kernel's, so every utterance gets bit for bit what lidbox_conv2d_fwd gives
+ *     it at B = 1, T = T_b, whatever its neighbours and its place.  The row -> (utterance, t) lookup runs in front of the
+ *     contraction loop: one binary search of row_offsets per tile, then steps over the borders inside it.  total_T * F < 2^31.
+ *   lidbox_conv2d_strided_ragged_fwd: the same for lidbox_conv2d_strided_fwd, for time geometries that keep the length
+ *     (pt0 + pt1 == kt - 1; anything else is LIDBOX_E_INVALID): y [total_T][Fo][C_out], bit-identical per utterance to the
+ *     dense call at B = 1.
+ *   lidbox_bn_maxpool2d_ragged_fwd: lidbox_bn_maxpool2d_fwd per utterance: the T_b / 2 pooled rows of utterance b (T_b from
+ *     in_offsets) go to the rows out_offsets[b] .. of y [total_out][F/2][C] (and argmax, which may be NULL); further rows of its
+ *     output segment are not touched (so a layout with pad rows can be written in place), an utterance with T_b = 1 writes
+ *     nothing.  Values, tie rule and codes are the dense kernel's, bit for bit.
+ * lidbox_bn_relu_fwd and lidbox_bn_relu_maxf_fwd are row-wise: they serve ragged images as they are (B = 1, T = total_T). */
+int lidbox_conv2d_ragged_fwd(const float* x, const long* row_offsets, int B, int total_T, int F, int C_in, const float* W, int k,
+                             int C_out, const float* bias, int relu, float* y, lidbox_stream_t stream);
+int lidbox_conv2d_strided_ragged_fwd(const float* x, const long* row_offsets, int B, int total_T, int F, int C_in, const float* W,
+                                     lidbox_conv2d_taps_t taps, int C_out, const float* bias, float* y, lidbox_stream_t stream);
+int lidbox_bn_maxpool2d_ragged_fwd(const float* x, const long* in_offsets, int B, int F, int C, const float* scale,
+                                   const float* shift, float* y, const long* out_offsets, long total_out, unsigned char* argmax,
+                                   lidbox_stream_t stream);
 /* kernel_regularizer=l2(lambda) (crnn.py:39) on `count` <= 16 tensors params[offsets[t] .. + sizes[t]): grads (may be NULL)
  * += 2 lambdas[t] grad_scale params, and loss[0] (may be NULL) += sum_t lambdas[t] sum params^2.  A fixed grid writes the
  * gradient and per-workgroup partial sums (workspace: lidbox_l2_penalty_workspace bytes, needed when loss != NULL), a

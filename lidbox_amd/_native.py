@@ -239,6 +239,9 @@ _SIGS = {
     "lidbox_bn_relu_bwd": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
     "lidbox_bn_relu_maxf_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp]),
     "lidbox_bn_relu_maxf_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp]),
+    "lidbox_conv2d_ragged_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "lidbox_conv2d_strided_ragged_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, Conv2DTaps, _i, _vp, _vp, _vp]),
+    "lidbox_bn_maxpool2d_ragged_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp]),
     "lidbox_seq_avg_pool_fwd": (_i, [_vp, _i, _i, _i, _l, _l, _f, _vp, _l, _vp]),
     "lidbox_seq_avg_pool_bwd": (_i, [_vp, _l, _i, _i, _i, _f, _vp, _l, _l, _i, _vp]),
     "lidbox_mla_attention_fwd": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp]),

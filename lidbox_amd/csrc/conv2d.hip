@@ -37,6 +37,9 @@
 // (TF's MaxPoolGrad and torch.nn.functional.max_pool2d) -- and the winner's code 2 * dfreq + dtime is kept for backward,
 // which gathers: each input cell takes its window's gradient when it is the recorded winner, zero otherwise (and zero for
 // the dropped cells).
+//
+// Ragged forward (inference on utterances of different lengths laid end to end): the forward kernels of both families and the
+// pool once more at the end of the file, with the time bounds and T / 2 of each row's own utterance; nothing above them changed.
 #include <stdint.h>
 
 #include <type_traits>
@@ -865,6 +868,205 @@ int ew_blocks(long n) {
     return (int)(b < 8192 ? b : 8192);
 }
 
+// ============================================================================================== ragged forward (inference)
+// The forward kernels above for B utterances of DIFFERENT lengths stored end to end: utterance b owns the image rows
+// off[b] .. off[b + 1] of x and y (no gaps, no halo), off an int64 device array of B + 1 entries rising from 0 that the
+// kernels trust.  Storage being contiguous, a pixel's address and its tap's offset are the dense ones with B = 1, T = total_T;
+// what changes is the bound a tap's time index is tested against: its own utterance's [0, T_b), looked up in front of the
+// contraction loop: one binary search of off per tile for its first row, from which each row steps over the borders in the tile.  Tiles, chunks and the k-chain of every output are the dense
+// kernels', so an utterance gets bit for bit what the dense call gives it at B = 1, T = T_b, wherever it lies and whatever
+// surrounds it; a tile may span several utterances and an utterance several tiles.  No atomics, nothing between workgroups.
+
+// the utterance that owns row r: the last b with off[b] <= r (0 <= r < off[B]; empty utterances are stepped over)
+__device__ __forceinline__ int rg_find(const long* __restrict__ off, int B, long r) {
+    int lo = 0, hi = B;                                // off[lo] <= r < off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= r)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// conv_fwd_kernel on [total_T][F][C]: g.B = utterances, g.T = total_T, g.M = total_T * F; grid (ceil(M / 128), Cout / BN)
+template <int BN>
+__global__ __launch_bounds__(256) void conv_ragged_fwd_kernel(const float* __restrict__ x, const long* __restrict__ off,
+                                                              const float* __restrict__ W, const float* __restrict__ bias,
+                                                              int relu, float* __restrict__ y, const ConvGeom g) {
+    constexpr int BQ = CV_KC * BN / 256;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long m0 = (long)blockIdx.x * CV_BM;
+    const int n0 = blockIdx.y * BN;
+    const int kk = tid & 15, r0 = tid >> 4;
+    int tt[8], tl[8], ff[8];                  // t inside the row's utterance, that utterance's length, f
+    bool rok[8];
+    // one search per tile, for its first image row (uniform: scalar loads); the thread's rows rise with j, so each steps on
+    // from the one before it, over the utterance borders inside the tile
+    int b = rg_find(off, g.B, m0 / g.F);
+    long lo = off[b], hi = off[b + 1];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long m = m0 + r0 + 16 * j;
+        rok[j] = m < g.M;
+        const long mm = rok[j] ? m : m0;
+        const long row = mm / g.F;
+        ff[j] = (int)(mm - row * g.F);
+        while (row >= hi && b + 1 < g.B) {    // an empty utterance is stepped over
+            ++b;
+            lo = hi;
+            hi = off[b + 1];
+        }
+        tt[j] = (int)(row - lo);
+        tl[j] = (int)(hi - lo);
+    }
+    float av[8], bv[BQ];
+    auto load = [&](int kc) {
+        const KTap tp = ktap(g, kc + kk);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int t2 = tt[j] + tp.dt, f2 = ff[j] + tp.df;
+            const bool ok = rok[j] && tp.ok && (unsigned)t2 < (unsigned)tl[j] && (unsigned)f2 < (unsigned)g.F;
+            av[j] = ok ? x[(m0 + r0 + 16 * j) * g.Cin + tp.delta] : 0.0f;
+        }
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+            bv[q] = kc + kr < g.K ? W[(long)(kc + kr) * g.Cout + n0 + n] : 0.0f;
+        }
+    };
+    f32x4 acc[2][BN / 16];
+    tile_clear<BN>(acc);
+    load(0);
+    tile_pipeline<BN, A_ROWS>(acc, av, bv, tid, w, lane, 0, g.K, load);
+    tile_walk<BN>(acc, w, lane, m0, n0, bias, [y, relu, M = g.M, Cout = g.Cout](long m, int n, float v, float bb) {
+        if (m >= M) return;
+        v += bb;
+        if (relu) v = fmaxf(v, 0.0f);
+        y[m * Cout + n] = v;
+    });
+}
+
+// sconv_kernel<BN, false> for a time geometry that keeps the length (pt0 + pt1 == kt - 1): g.B = utterances, g.T = g.To =
+// total_T; a tile is 128 rows (utterance, t) of one output column.  grid (ceil(total_T / 128), Fo, Cout / BN)
+template <int BN>
+__global__ __launch_bounds__(256) void sconv_ragged_kernel(const float* __restrict__ x, const long* __restrict__ off,
+                                                           const float* __restrict__ W, const float* __restrict__ bias,
+                                                           float* __restrict__ y, const SGeom g) {
+    constexpr int BQ = CV_KC * BN / 256;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int col = blockIdx.y;
+    const int n0 = blockIdx.z * BN;
+    const long R = g.To;
+    const long r0t = (long)blockIdx.x * CV_BM;
+    const int f0 = col * g.sf - g.pf;
+    const int j0 = max(0, -f0), nj = max(0, min(g.kf, g.F - f0) - j0);
+    const int Kv = g.kt * nj * g.Cin;
+    const int kk = tid & 15, r0 = tid >> 4;
+    int tt[8], tl[8];
+    bool rok[8];
+    int b = rg_find(off, g.B, r0t);           // one search per tile (uniform), then steps over the borders inside the tile
+    long lo = off[b], hi = off[b + 1];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long r = r0t + r0 + 16 * j;
+        rok[j] = r < R;
+        const long rr = rok[j] ? r : r0t;
+        while (rr >= hi && b + 1 < g.B) {
+            ++b;
+            lo = hi;
+            hi = off[b + 1];
+        }
+        tt[j] = (int)(rr - lo);
+        tl[j] = (int)(hi - lo);
+    }
+    auto split = [&](int v, int& i, int& m, int& c) {
+        c = v % g.Cin;
+        const int q = v / g.Cin;
+        if (g.tfirst) {
+            i = q / nj;
+            m = q - i * nj;
+        } else {
+            m = q / g.kt;
+            i = q - m * g.kt;
+        }
+    };
+    float av[8], bv[BQ];
+    auto load = [&](int kc) {
+        const int v = kc + kk;
+        const bool vok = v < Kv;
+        int i, m, c;
+        split(vok ? v : 0, i, m, c);
+        const int f2 = col * g.sf + j0 + m - g.pf;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int t2 = tt[s] + i - g.pt;
+            const bool ok = vok && rok[s] && (unsigned)t2 < (unsigned)tl[s];
+            av[s] = ok ? x[((r0t + r0 + 16 * s + i - g.pt) * g.F + f2) * g.Cin + c] : 0.0f;
+        }
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) {
+            const int e = tid + 256 * q, kr = e / BN, n = e - kr * BN;
+            const int v2 = kc + kr;
+            float wv = 0.0f;
+            if (v2 < Kv) {
+                int i2, m2, c2;
+                split(v2, i2, m2, c2);
+                const long tap = sg_tap(g, i2, j0 + m2);
+                wv = W[(tap * g.Cin + c2) * g.Cout + n0 + n];
+            }
+            bv[q] = wv;
+        }
+    };
+    f32x4 acc[2][BN / 16];
+    tile_clear<BN>(acc);
+    if (Kv > 0) load(0);
+    tile_pipeline<BN, A_ROWS>(acc, av, bv, tid, w, lane, 0, Kv, load);
+    tile_walk<BN>(acc, w, lane, r0t, n0, bias, [y, R, Fo = g.Fo, col, Cout = g.Cout](long row, int n, float v, float bb0) {
+        if (row >= R) return;
+        y[(row * Fo + col) * Cout + n] = v + bb0;
+    });
+}
+
+// bn_maxpool_fwd_kernel per utterance: output row q of y [total_out][F / 2][C] belongs to the utterance b whose output
+// segment oof[b] .. oof[b + 1] holds it, and is written when it is one of that utterance's T_b / 2 pooled rows (the rest of
+// a segment is left alone).  code may be NULL.
+__global__ __launch_bounds__(256) void bn_maxpool_ragged_fwd_kernel(const float* __restrict__ x, const long* __restrict__ iof,
+                                                                    int B, int F, int C, const float* __restrict__ scale,
+                                                                    const float* __restrict__ shift, float* __restrict__ y,
+                                                                    const long* __restrict__ oof, uint8_t* __restrict__ code,
+                                                                    long n) {
+    const long i = blockIdx.x * 256L + threadIdx.x;
+    if (i >= n) return;
+    const int F2 = F / 2;
+    const int c = (int)(i % C);
+    long q = i / C;
+    const int f2 = (int)(q % F2);
+    q /= F2;
+    // one search per workgroup, for the row of its first element (uniform), then steps on to this element's row
+    int b = rg_find(oof, B, blockIdx.x * 256L / ((long)F2 * C));
+    while (b + 1 < B && oof[b + 1] <= q) ++b;
+    const long t2 = q - oof[b];
+    const long ilo = iof[b];
+    if (t2 < 0 || t2 >= (iof[b + 1] - ilo) / 2) return;
+    const float* p = x + (((ilo + 2 * t2) * F) + 2 * f2) * C + c;
+    const float sc = scale[c], sh = shift[c];
+    const long off[4] = {0, (long)F * C, C, (long)F * C + C};
+    float best = p[off[0]] * sc + sh;
+    int bc = 0;
+#pragma unroll
+    for (int e = 1; e < 4; ++e) {
+        const float v = p[off[e]] * sc + sh;
+        if (v > best) {
+            best = v;
+            bc = e;
+        }
+    }
+    y[i] = best;
+    if (code) code[i] = (uint8_t)bc;
+}
+
 }  // namespace
 
 extern "C" int lidbox_conv2d_fwd(const float* x, int B, int T, int F, int C_in, const float* W, int k, int C_out,
@@ -1064,6 +1266,59 @@ extern "C" int lidbox_bn_relu_maxf_bwd(const float* x, int B, int T, int F, int 
     if (n == 0) return LIDBOX_OK;
     hipLaunchKernelGGL(bn_relu_maxf_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, T, F, C, scale, shift, dy,
                        dy_batch_stride, dx, n);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- ragged forward entry points
+extern "C" int lidbox_conv2d_ragged_fwd(const float* x, const long* row_offsets, int B, int total_T, int F, int C_in,
+                                        const float* W, int k, int C_out, const float* bias, int relu, float* y,
+                                        lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && total_T >= 0, "B >= 0, total_T >= 0");
+    if (int e = conv_check(__func__, 1, total_T > 0 ? total_T : 1, F, C_in, C_out, k)) return e;
+    LBX_ARG(x && row_offsets && W && y, "x, row_offsets, W, y != NULL");
+    if (B == 0 || total_T == 0) return LIDBOX_OK;
+    const ConvGeom g{B, total_T, F, C_in, C_out, k, (k - 1) / 2, (long)total_T * F, k * k * C_in};
+    const int bn = conv_tile_n(C_out), r = relu ? 1 : 0;
+    const dim3 grid((unsigned)lbx_cdiv(g.M, CV_BM), (unsigned)(C_out / bn));
+    hipStream_t st = (hipStream_t)stream;
+    with_tile_n(bn, [&](auto BN) {
+        hipLaunchKernelGGL(conv_ragged_fwd_kernel<BN()>, grid, dim3(256), 0, st, x, row_offsets, W, bias, r, y, g);
+    });
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_conv2d_strided_ragged_fwd(const float* x, const long* row_offsets, int B, int total_T, int F, int C_in,
+                                                const float* W, lidbox_conv2d_taps_t taps, int C_out, const float* bias,
+                                                float* y, lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && total_T >= 0, "B >= 0, total_T >= 0");
+    if (int e = sconv_check(__func__, 1, total_T > 0 ? total_T : 1, F, C_in, C_out, taps)) return e;
+    LBX_ARG(taps.pt0 + taps.pt1 == taps.kt - 1, "a time geometry that keeps the length: pt0 + pt1 == kt - 1");
+    LBX_ARG(x && row_offsets && W && y, "x, row_offsets, W, y != NULL");
+    if (B == 0 || total_T == 0) return LIDBOX_OK;
+    SGeom g = sgeom(1, total_T, F, C_in, C_out, taps);
+    g.B = B;
+    const int bn = conv_tile_n(C_out);
+    const dim3 grid((unsigned)lbx_cdiv(total_T, CV_BM), (unsigned)g.Fo, (unsigned)(C_out / bn));
+    hipStream_t st = (hipStream_t)stream;
+    with_tile_n(bn, [&](auto BN) {
+        hipLaunchKernelGGL(sconv_ragged_kernel<BN()>, grid, dim3(256), 0, st, x, row_offsets, W, bias, y, g);
+    });
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_bn_maxpool2d_ragged_fwd(const float* x, const long* in_offsets, int B, int F, int C, const float* scale,
+                                              const float* shift, float* y, const long* out_offsets, long total_out,
+                                              unsigned char* argmax, lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && F >= 2 && C >= 1 && total_out >= 0 && total_out < (1L << 31) && total_out * (F / 2) * C < (1L << 38),
+            "B >= 0, F >= 2, C >= 1, total_out >= 0, sizes in range");
+    LBX_ARG(x && in_offsets && scale && shift && y && out_offsets, "pointers != NULL (argmax may be)");
+    const long n = total_out * (F / 2) * C;
+    if (B == 0 || n == 0) return LIDBOX_OK;
+    hipLaunchKernelGGL(bn_maxpool_ragged_fwd_kernel, dim3((unsigned)lbx_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x,
+                       in_offsets, B, F, C, scale, shift, y, out_offsets, argmax, n);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

@@ -32,7 +32,8 @@ import numpy as np
 
 
 class RaggedPlan:
-    """pads [n+1], cum [n+1], T [n+1][B] (frames per level and utterance), L [B], off [B+1] (top-level rows, int64) and rows [n+1] = M_i"""
+    """pads [n+1], cum [n+1], T [n+1][B] (frames per level and utterance), L [B], off [B+1] (top-level rows, int64) and rows [n+1] = M_i;
+    lead [n+1]: the part of pads[i] that is not the reading conv's causal padding (ragged_plan's extra_pads; zeros without)"""
 
     def __init__(self, pads, cum, T, L, off):
         self.pads, self.cum, self.T, self.L, self.off = pads, cum, T, L, off
@@ -47,8 +48,12 @@ class RaggedPlan:
         return int(self.T[i].sum())
 
 
-def ragged_plan(lengths, convs):
-    """lengths: frames per utterance (each >= 1); convs: (kernel, stride) pairs or objects with .k and .s.  Returns a RaggedPlan."""
+def ragged_plan(lengths, convs, extra_pads=None):
+    """lengths: frames per utterance (each >= 1); convs: (kernel, stride) pairs or objects with .k and .s.  Returns a RaggedPlan.
+    extra_pads {level: (before, after)} asks for further pad rows around an utterance's frames at a level, for a layer that runs
+    on that level in place (clstm's LSTM on level 3: one row each side, the [pad, frames, pad] segments of `recurrent_plan`):
+    pads[level] grows by `before`, so the frames start that much deeper in the segment and the conv that reads the level must
+    start its windows `before` rows on (plan.lead[level]), and the segment has room for `after` rows behind the frames."""
     ks = [(int(c.k), int(c.s)) if hasattr(c, "k") else (int(c[0]), int(c[1])) for c in convs]
     if any(k < 1 or s < 1 for k, s in ks):
         raise ValueError("kernel sizes and strides must be >= 1")
@@ -63,11 +68,19 @@ def ragged_plan(lengths, convs):
     T = [T0]
     for _, s in ks:
         T.append((T[-1] - 1) // s + 1)
+    lead, after = [0] * (n + 1), [0] * (n + 1)
+    for i, (p0, p1) in (extra_pads or {}).items():
+        if not 0 <= int(i) <= n or p0 < 0 or p1 < 0:
+            raise ValueError("extra_pads: levels 0 .. %d, pads >= 0" % n)
+        lead[i], after[i] = int(p0), int(p1)
+        pads[i] += int(p0)
     L = np.zeros(len(T0), np.int64)
     for i in range(n + 1):
-        L = np.maximum(L, -(-(pads[i] + T[i]) // cum[i]))
+        L = np.maximum(L, -(-(pads[i] + T[i] + after[i]) // cum[i]))
     off = np.concatenate(([0], np.cumsum(L))).astype(np.int64)
-    return RaggedPlan(pads, cum, T, L, off)
+    plan = RaggedPlan(pads, cum, T, L, off)
+    plan.lead = lead
+    return plan
 
 
 class RecurrentPlan:

@@ -25,6 +25,21 @@ from .flat import _rows
 from .ragged import recurrent_plan
 
 
+def ragged_input(X, row_offsets, C):
+    """the checks a ragged pass makes of its arguments (X [total_T, C] float32, contiguous, on the HIP device; row_offsets rising
+    from 0 to total_T, no empty utterance); returns (X, the offsets as int64 [B + 1], the lengths [B])"""
+    X = nv.require_gpu_tensor(X, "X", torch.float32)
+    if X.dim() != 2 or X.shape[1] != C or not X.is_contiguous():
+        raise ValueError("expected a contiguous input [total_T, %d], got %s" % (C, tuple(X.shape)))
+    ro = np.ascontiguousarray(np.asarray(row_offsets, np.int64).reshape(-1))
+    if len(ro) < 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or int(ro[-1]) != X.shape[0]:
+        raise ValueError("row_offsets must rise from 0 to the %d rows of X" % X.shape[0])
+    lengths = np.diff(ro)
+    if (lengths < 1).any():
+        raise ValueError("utterance %d has length 0: every utterance needs at least one frame" % int(np.flatnonzero(lengths < 1)[0]))
+    return X, ro, lengths
+
+
 class RaggedRecurrentWorkspace:
     """Device buffers of the ragged recurrent pass, sized by capacity: `cap_rows` rows (frames + 2 per utterance) and `cap_B`
     utterances; a pass with fewer of either uses the front of every buffer.  The engine's `_ragged_buffers_rows(cap_rows)` /
@@ -50,14 +65,19 @@ class RaggedRecurrentWorkspace:
 
 class RaggedPlanOnDevice:
     """the plan's arrays in one int64 device tensor: ro [B + 1] (the caller's row offsets), seg [B + 1], slots [3, B], first [B]
-    (row of every utterance's first frame) and lengths [B], as pointers"""
+    (row of every utterance's first frame) and lengths [B], as pointers; `extra`: see below"""
 
-    def __init__(self, plan, ro, device):
+    def __init__(self, plan, ro, device, extra=()):
         B = plan.B
-        host = np.concatenate([ro, plan.seg, plan.slots().reshape(-1), plan.seg[:-1] + 1, plan.lengths]).astype(np.int64)
+        host = np.concatenate([ro, plan.seg, plan.slots().reshape(-1), plan.seg[:-1] + 1, plan.lengths] + list(extra)).astype(np.int64)
         self.tensor = torch.from_numpy(host).to(device)
         at = lambda words: ctypes.c_void_p(self.tensor.data_ptr() + 8 * words)
         self.ro, self.seg, self.slots, self.first, self.lengths = at(0), at(B + 1), at(2 * B + 2), at(5 * B + 2), at(6 * B + 2)
+        # further int64 arrays of the caller's (the conv-recurrent pass: the offsets of its pooled levels), same upload
+        self.extra, words = [], 7 * B + 2
+        for e in extra:
+            self.extra.append(at(words))
+            words += len(e)
         self.sorted_lengths = ctypes.c_void_p(plan.sorted_lengths.ctypes.data)       # host array, read by the launcher
 
 
@@ -70,13 +90,22 @@ class RaggedRecurrent:
             return "the ragged pass computes in float32 only, this model has compute_dtype=%r" % (self.compute_dtype,)
         return None
 
+    ragged_workspace_class = RaggedRecurrentWorkspace
+
     def ragged_workspace(self, rows, B):
         """the model's one RaggedRecurrentWorkspace, with room for `rows` rows and B utterances"""
         ws = getattr(self, "_rws", None)
         if ws is None:
-            ws = self._rws = RaggedRecurrentWorkspace(self)
+            ws = self._rws = self.ragged_workspace_class(self)
         ws.reserve(self, rows, B)
         return ws
+
+    def _ragged_input(self, X, row_offsets):
+        """the model's refusal, then `ragged_input`"""
+        reason = self.ragged_refusal()
+        if reason:
+            raise ValueError(reason)
+        return ragged_input(X, row_offsets, self.input_dim)
 
     def forward_ragged(self, X, row_offsets, upto_embedding=False):
         """Inference on utterances of different lengths in one pass.  X [total_T, C] float32, contiguous, on the HIP device;
@@ -84,18 +113,7 @@ class RaggedRecurrent:
         SequentialTDNN.forward_ragged).  Returns a view of the workspace, [B, D]: the model output or, upto_embedding, the
         model's embedding (`_ragged_embedding_dim` has its width) -- what the dense pass gives each utterance alone, up to the
         rounding of another GEMM / pooling path."""
-        reason = self.ragged_refusal()
-        if reason:
-            raise ValueError(reason)
-        X = nv.require_gpu_tensor(X, "X", torch.float32)
-        if X.dim() != 2 or X.shape[1] != self.input_dim or not X.is_contiguous():
-            raise ValueError("expected a contiguous input [total_T, %d], got %s" % (self.input_dim, tuple(X.shape)))
-        ro = np.ascontiguousarray(np.asarray(row_offsets, np.int64).reshape(-1))
-        if len(ro) < 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or int(ro[-1]) != X.shape[0]:
-            raise ValueError("row_offsets must rise from 0 to the %d rows of X" % X.shape[0])
-        lengths = np.diff(ro)
-        if (lengths < 1).any():
-            raise ValueError("utterance %d has length 0: every utterance needs at least one frame" % int(np.flatnonzero(lengths < 1)[0]))
+        X, ro, lengths = self._ragged_input(X, row_offsets)
         B = len(lengths)
         with torch.cuda.device(self.device):
             if B == 0:
@@ -136,4 +154,4 @@ class RaggedRecurrent:
                                                None if hlast is None else nv.ptr(hlast), nv.current_stream()))
 
 
-__all__ = ["RaggedRecurrent", "RaggedRecurrentWorkspace", "RaggedPlanOnDevice"]
+__all__ = ["RaggedRecurrent", "RaggedRecurrentWorkspace", "RaggedPlanOnDevice", "ragged_input"]
