@@ -795,7 +795,9 @@ int lidbox_dropout_rows(lidbox_rows_out_t x, int C, float rate, unsigned long lo
 /* Keras SpatialDropout1D (xvector.py:50-51, cnn.py:29-30) in place on x [B, T, C] (batch stride in floats): whole
  * channels of an utterance are zeroed with probability `rate`, kept ones scaled by 1/(1-rate).  The mask is a
  * counter-based hash of (seed, *step_counter, b, c); step_counter is a DEVICE int64 (NULL = 0), e.g. the Adam step,
- * so a replayed hipGraph draws a fresh mask per step.  mask_out: optional [B, C] copy of the applied factors. */
+ * so a replayed hipGraph draws a fresh mask per step.  mask_out: optional [B, C] copy of the applied factors.
+ * rate == 0 (like B == 0 or T == 0) returns before any launch: x AND mask_out are left exactly as they were, so a caller
+ * that wants the all-ones mask of rate 0 fills mask_out itself. */
 int lidbox_spatial_dropout(float* x, int B, int T, int C, long batch_stride, float rate,
                            unsigned long long seed, const void* step_counter, float* mask_out,
                            lidbox_stream_t stream);
