@@ -1054,6 +1054,19 @@ int lidbox_seq_avg_pool_bwd(const float* dout, long ldo, int B, int T, int C, fl
 int lidbox_mla_attention_fwd(const float* z, int B, int T, int K, float* att, long ld_att, float* colsum, lidbox_stream_t stream);
 int lidbox_mla_attention_bwd(const float* z, const float* att, long ld_att, const float* colsum, const float* datt, long ld_datt,
                              int B, int T, int K, float* dz, lidbox_stream_t stream);
+/* lidbox_mla_attention_fwd on B utterances of different lengths that lie end to end (inference: there is no ragged backward):
+ *   z            [total_T][K]: utterance b owns the rows row_offsets[b] .. row_offsets[b + 1]
+ *   row_offsets  device int64 [B + 1], rising from 0.  Every utterance has at least one row and fewer than 2^31; the kernel
+ *                trusts both, as lidbox_stats_pool_ragged_fwd trusts lengths[b] >= 1
+ *   att          rows ld_att >= K floats apart, as above: the levels write column slices of one [B][L K] buffer
+ *   colsum       [B][K], may be NULL: the sums s are then not stored (nothing but a backward pass reads them)
+ * One workgroup per utterance running the dense kernel's own code on its rows (same row slots, same shuffle and LDS combine,
+ * same final division), so att[b] and colsum[b] are bit for bit what lidbox_mla_attention_fwd gives at B = 1, T = T_b on
+ * z + row_offsets[b] K, whatever the neighbours and the place in the batch.  The load path is chosen once, as in the dense
+ * call: 16-byte loads when K % 4 == 0 and z is 16-byte aligned (every utterance's first row then is), scalar ones otherwise.
+ * No atomics, no communication between workgroups.  1 <= K <= 1024; B == 0 returns without a launch. */
+int lidbox_mla_attention_ragged_fwd(const float* z, const long* row_offsets, long B, int K, float* att, long ld_att, float* colsum,
+                                    lidbox_stream_t stream);
 /* BatchNormalization apply -> ReLU -> Dropout(rate) on x viewed as [R][C] in one pass (DenseBlock, multilevel_attention.py:53-57):
  * y = relu(x * scale[c] + shift[c]) * mask, mask = 0 with probability `rate` and 1 / (1 - rate) otherwise, drawn from
  * (seed, *step_counter, r, c) exactly as lidbox_dropout_rows draws it (step_counter: device int64, NULL reads 0).

@@ -1,6 +1,7 @@
 // mla.hip -- kernels of the multi-level attention classifier (lidbox_amd.models.multilevel_attention, reference
 // lidbox/models/multilevel_attention.py:21-85; Yu et al. 2018):
-//   * the attention pooling of one level and its backward pass (lidbox_mla_attention_fwd / _bwd);
+//   * the attention pooling of one level and its backward pass (lidbox_mla_attention_fwd / _bwd), and the forward pooling of
+//     utterances of different lengths that lie end to end (lidbox_mla_attention_ragged_fwd: the same per-utterance code);
 //   * BatchNormalization-apply + ReLU + Dropout over [R, C] activations in one pass, forward and backward
 //     (lidbox_bn_relu_dropout_fwd / _bwd), bit-identical to lidbox_bn_relu_* composed with lidbox_dropout_rows.
 //
@@ -99,15 +100,30 @@ __device__ __forceinline__ float sigmoidf_(float x, float* dv = nullptr) {
     return x >= 0.f ? r : u * r;
 }
 
-// grid (B), block NW * 64 (16 waves, 8 for the widest rows: mla_plan), dynamic LDS NW * 2 * K floats
-template <int VEC, int NJ>
-__global__ __launch_bounds__(VEC * NJ >= 16 ? 512 : 1024) void mla_attention_fwd_kernel(const float* __restrict__ z, int T, int K, int G, float* __restrict__ att,
-                                                                 long ld_att, float* __restrict__ colsum) {
+// acc + c v of the forward pass, with its rounding written down.  Under -ffp-contract=fast the compiler may fuse `acc += c * v`
+// or not, and it chose per instantiation: one fma everywhere except in <4,2> and <4,4>, where the product is rounded first.
+// Those are the bits the dense kernel has always given, so they are pinned here: the dense and the ragged kernel are separate
+// compilations of the same function, and left to the optimiser they need not agree (nor stay as they were).
+template <bool FUSED>
+__device__ __forceinline__ float mla_acc_cv(float acc, float c, float v) {
+    if constexpr (FUSED) {
+        return fmaf(c, v, acc);
+    } else {
+#pragma clang fp contract(off)
+        const float cv = c * v;
+        return acc + cv;
+    }
+}
+
+// One utterance's pooling, by the whole workgroup: zb [T, K] -> att_b [K] and, unless COLSUM_OPT and colsum_b is NULL, colsum_b [K].
+// The dense and the ragged forward kernel both call it, so an utterance's bits are those of (T, K) in either.
+// block NW * 64, dynamic LDS NW * 2 * K floats
+template <int VEC, int NJ, bool COLSUM_OPT>
+__device__ __forceinline__ void mla_attention_utterance(const float* __restrict__ zb, int T, int K, int G, float* __restrict__ att_b,
+                                                        float* __restrict__ colsum_b) {
     extern __shared__ float lds[];
-    const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, NW = blockDim.x >> 6;
     const int rpw = 64 / G, slot = lane / G, gl = lane - slot * G;
-    const float* zb = z + (long)b * T * K;
     float zr[NJ][VEC], pr[NJ][VEC], accS[NJ][VEC], accV[NJ][VEC];
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
@@ -126,7 +142,7 @@ __global__ __launch_bounds__(VEC * NJ >= 16 ? 512 : 1024) void mla_attention_fwd
                     if ((gl + G * j) * VEC + e < K) {
                         const float c = fminf(fmaxf(pr[j][e], MLA_CLIP_LO), MLA_CLIP_HI);
                         accS[j][e] += c;
-                        accV[j][e] += c * sigmoidf_(zr[j][e]);
+                        accV[j][e] = mla_acc_cv<!(VEC == 4 && NJ >= 2)>(accV[j][e], c, sigmoidf_(zr[j][e]));
                     }
         }
     }
@@ -152,9 +168,28 @@ __global__ __launch_bounds__(VEC * NJ >= 16 ? 512 : 1024) void mla_attention_fwd
             s += lds[(i * 2 + 0) * K + k];
             sv += lds[(i * 2 + 1) * K + k];
         }
-        att[(long)b * ld_att + k] = sv / s;
-        colsum[(long)b * K + k] = s;
+        att_b[k] = sv / s;
+        if (!COLSUM_OPT || colsum_b) colsum_b[k] = s;
     }
+}
+
+// grid (B), block NW * 64 (16 waves, 8 for the widest rows: mla_plan), dynamic LDS NW * 2 * K floats
+template <int VEC, int NJ>
+__global__ __launch_bounds__(VEC * NJ >= 16 ? 512 : 1024) void mla_attention_fwd_kernel(const float* __restrict__ z, int T, int K, int G, float* __restrict__ att,
+                                                                 long ld_att, float* __restrict__ colsum) {
+    const int b = blockIdx.x;
+    mla_attention_utterance<VEC, NJ, false>(z + (long)b * T * K, T, K, G, att + (long)b * ld_att, colsum + (long)b * K);
+}
+
+// the same on utterances that lie end to end: z [total_T, K], utterance b = rows row_offsets[b] .. row_offsets[b + 1] (at least
+// one); colsum may be NULL.  grid (B), block and LDS as above
+template <int VEC, int NJ>
+__global__ __launch_bounds__(VEC * NJ >= 16 ? 512 : 1024) void mla_attention_ragged_fwd_kernel(const float* __restrict__ z, const long* __restrict__ row_offsets, int K, int G,
+                                                                        float* __restrict__ att, long ld_att, float* __restrict__ colsum) {
+    const int b = blockIdx.x;
+    const long r0 = row_offsets[b];
+    const int T = (int)(row_offsets[b + 1] - r0);
+    mla_attention_utterance<VEC, NJ, true>(z + r0 * K, T, K, G, att + (long)b * ld_att, colsum ? colsum + (long)b * K : nullptr);
 }
 
 // dp = m g (v - att) / s,  dz = p (dp - sum_j dp_j p_j) + g (c / s) v (1 - v),  m = (lo <= p <= hi)
@@ -286,6 +321,13 @@ void launch_fwd(const MlaPlan& p, hipStream_t st, const float* z, int B, int T, 
 }
 
 template <int VEC, int NJ>
+void launch_ragged_fwd(const MlaPlan& p, hipStream_t st, const float* z, const long* row_offsets, long B, int K, float* att, long ld_att,
+                       float* colsum) {
+    hipLaunchKernelGGL((mla_attention_ragged_fwd_kernel<VEC, NJ>), dim3((unsigned)B), dim3(p.nw * 64), (size_t)p.nw * 2 * K * sizeof(float), st,
+                       z, row_offsets, K, p.G, att, ld_att, colsum);
+}
+
+template <int VEC, int NJ>
 void launch_bwd(const MlaPlan& p, hipStream_t st, const float* z, const float* att, long ld_att, const float* colsum, const float* datt,
                 long ld_datt, int B, int T, int K, float* dz) {
     const int nw = 8;
@@ -321,6 +363,32 @@ extern "C" int lidbox_mla_attention_fwd(const float* z, int B, int T, int K, flo
         else MLA_FWD(1, 16);
     }
 #undef MLA_FWD
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_mla_attention_ragged_fwd(const float* z, const long* row_offsets, long B, int K, float* att, long ld_att,
+                                               float* colsum, lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && B <= 0x7fffffffL && K >= 1, "0 <= B < 2^31, K >= 1");
+    LBX_ARG(K <= MLA_MAX_K, "K <= 1024");
+    LBX_ARG(z && row_offsets && att, "z, row_offsets, att != NULL");
+    LBX_ARG(ld_att >= K, "ld_att >= K");
+    if (B == 0) return LIDBOX_OK;
+    const MlaPlan p = mla_plan(K, K % 4 == 0 && aligned16(z));        // r0 K floats on: a multiple of 16 bytes when K % 4 == 0
+    hipStream_t st = (hipStream_t)stream;
+#define MLA_RFWD(V, N) launch_ragged_fwd<V, N>(p, st, z, row_offsets, B, K, att, ld_att, colsum)
+    if (p.vec == 4) {
+        if (p.nj == 1) MLA_RFWD(4, 1);
+        else if (p.nj == 2) MLA_RFWD(4, 2);
+        else MLA_RFWD(4, 4);
+    } else {
+        if (p.nj == 1) MLA_RFWD(1, 1);
+        else if (p.nj == 2) MLA_RFWD(1, 2);
+        else if (p.nj == 4) MLA_RFWD(1, 4);
+        else if (p.nj == 8) MLA_RFWD(1, 8);
+        else MLA_RFWD(1, 16);
+    }
+#undef MLA_RFWD
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

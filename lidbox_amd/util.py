@@ -43,7 +43,7 @@ def predict_with_model(model, ds, predict_fn=None):
 def predict_ragged_with_model(model, ds, launch_batch=256):
     """`predict_with_model` for utterances of different lengths (no reference counterpart): `ds` yields ELEMENTS, dicts with `id` and
     `input` ([T, C], any T); up to `launch_batch` consecutive ones go through one ragged pass (`model.predict_ragged`: the x-vector family and
-    the recurrent models lstm, ap_lstm, bi_gru, spherespeaker, and crnn and clstm).  Returns the DataFrame `predict_with_model` returns."""
+    the recurrent models lstm, ap_lstm, bi_gru, spherespeaker, crnn and clstm, and multilevel_attention).  Returns the DataFrame `predict_with_model` returns."""
     launch_batch = int(launch_batch)
     if launch_batch < 1:
         raise ValueError("launch_batch must be at least 1")
