@@ -547,11 +547,11 @@ def extract_embeddings(ds, config):
     [B, D].  The embeddings of several extractors are concatenated on axis 1 (steps.py:693).  Elements of one batch
     must share the input shape (tf.data's `batch` has the same requirement).
     `ragged: true` (lidbox_amd only): up to `batch_size` consecutive elements whose [T, C] inputs may differ in T go through ONE
-    ragged pass per extractor (SequentialTDNN.embed_ragged; models/rnn_ragged.py for lstm, ap_lstm, bi_gru and spherespeaker;
-    ConvRecurrentModel.embed_ragged for crnn, whose utterances need 32 frames at least; CLSTM.embed_ragged for clstm;
-    MultilevelAttentionModel.embed_ragged for multilevel_attention); order
-    is kept and every element gets what `batch_size: 1` gives it up to rounding.  Every extractor must have a ragged form (`.ragged` of an as_embedding_extractor result, `.embed_ragged` of a
-    model); `no_unbatch` has no meaning without one input shape and is refused."""
+    ragged pass per extractor (`embed_ragged` of models/ragged_pass.py's RaggedPass, the base of every model with such a pass:
+    the x-vector family, lstm, ap_lstm, bi_gru, spherespeaker, crnn -- whose utterances need 32 frames at least -- clstm and
+    multilevel_attention); order is kept and every element gets what `batch_size: 1` gives it up to rounding.  Every
+    extractor must have a ragged form (`.ragged` of an as_embedding_extractor result, `.embed_ragged` of a model);
+    `no_unbatch` has no meaning without one input shape and is refused."""
     ragged = bool(config.get("ragged", False))
     no_unbatch = bool(config.get("no_unbatch", False))
     if ragged and no_unbatch:

@@ -6,6 +6,7 @@ BatchNormalization -> Dense(1024, relu) `fc_relu_2` -> BatchNormalization -> Den
 Built on the GRU engine of `lidbox_amd.models.gru_rnn`.
 """
 from .gru_rnn import BatchNormSpec, DenseSpec, GRUModel, GRUSpec
+from .ragged_pass import EmbeddingExtractor
 
 
 def create(input_shape, num_outputs, output_activation="log_softmax", channel_dropout_rate=0, seed=None, device=None,
@@ -25,21 +26,6 @@ def create(input_shape, num_outputs, output_activation="log_softmax", channel_dr
 loader = create      # lidbox/models/keras_utils.py:134 calls `model_module.loader(...)`
 
 
-class EmbeddingExtractor:
-    """reference bi_gru.py:20-23: the output of `fc_relu_1` with its activation removed, in inference mode"""
-
-    def __init__(self, model):
-        self.model = model
-
-    def __call__(self, x, training=False):
-        return self.model.embed(x)
-
-    predict = __call__
-
-    def ragged(self, X, row_offsets):
-        """the embeddings [B, num_fc_units] of B utterances of different lengths (GRUModel.embed_ragged)"""
-        return self.model.embed_ragged(X, row_offsets)
-
-
 def as_embedding_extractor(model):
+    """reference bi_gru.py:20-23: the output of `fc_relu_1` with its activation removed, in inference mode, [B, num_fc_units]"""
     return EmbeddingExtractor(model)

@@ -26,6 +26,11 @@ Parameters: one flat fp32 buffer in Keras layouts, in the order conv2d_1, conv2d
 lstm, frame4, frame5, Wf_1, Wf_2, segment1, segment2, output, so that the Trainer's default bucketed gradient exchange stays
 correct: every bucket boundary is a frame layer's kernel, and each parameter's gradient is final before the stage that
 completes its bucket ends.  BatchNormalization moving statistics live in `state`.  fp32 only.
+
+Ragged pass (inference): `_ragged_pass` composes SequentialTDNN's helpers (upload, pack, conv, pool and head) with the 2-D
+front-end in front of the pack, the LSTM on level 3 in front of frame4 and the attention in front of the pool; the buffers of
+the LSTM and the attention are sized off the level buffers and live and die with them (`_ragged_buffers_rows`), the
+front-end's are sized by the capacity `frames`.
 """
 import ctypes
 
@@ -34,6 +39,7 @@ import torch
 
 from .. import _native as nv
 from .flat import BatchNormSpec, FlatParams, LSTMLayer, _rows, lstm_layer_bwd, lstm_layer_fwd
+from .ragged import ragged_plan, recurrent_plan
 from .tdnn import DenseSpec, FreqAttentionSpec, SequentialTDNN, _Workspace as _TDNNWorkspace
 from .xvector import frame_layer, segment_layer
 
@@ -321,36 +327,41 @@ class CLSTM(SequentialTDNN):
         nv.check(lib.lidbox_conv2d_strided_wgrad(nv.ptr(ws.fe_in), nv.ptr(ws.cv_dz[0]), B, T, F0, 1, C1, tp1, self._p(n1 + ".W", True),
                                                  self._p(n1 + ".b", True), wws, wws_n, st))
 
-    # ------------------------------------------------------------------ ragged pass (inference, float32)
+    # ------------------------------------------------------------ ragged pass (inference, float32; models/ragged_pass.py)
     def ragged_refusal(self):
         """None for every flag combination: this module runs what SequentialTDNN's ragged pass leaves out (the 2-D front-end,
         the LSTM between frame3 and frame4, the frequency attention)"""
         return None
 
-    def _ragged_extras(self, ws, total_T):
-        """the buffers the flags add to SequentialTDNN's ragged workspace: per input frame (front-end) and per row of level 3
-        (LSTM) / of the pooling level (attention); replaced when the base workspace or the frame count outgrew them"""
+    def _ragged_plan(self, ro, lengths):
+        """use_lstm: level 3 carries a pad row before and after each utterance's frames, for the LSTM that runs there in place"""
+        plan = ragged_plan(lengths, self.convs, {3: (1, 1)} if self.use_lstm else None)
+        return plan, dict(rows=int(plan.off[-1]), B=plan.B, frames=int(ro[-1]))
+
+    def _ragged_buffers_rows(self, cap):
+        """SequentialTDNN's levels plus, per row of level 3, the LSTM's buffers and, per row of the pooling level, the
+        attention's"""
         f32 = dict(dtype=torch.float32, device=self.device)
-        if self.use_conv2d and total_T > getattr(ws, "cl_cap_T", 0):
-            cap = ws.cl_cap_T = max(int(total_T), getattr(ws, "cl_cap_T", 0) * 3 // 2)
-            (_, F1, _), (_, F2, _) = self.fe_geom
-            C1, C2 = self.filters
-            ws.cv_y = [torch.zeros((cap, F1, C1), **f32), torch.zeros((cap, F2, C2), **f32)]
-            ws.cv_a1 = torch.zeros((cap, F1, C1), **f32)
-            ws.cv_out = torch.zeros((cap, C2), **f32)
-            ws.cv_c = [torch.zeros((4, C1), **f32), torch.zeros((4, C2), **f32)]
-        if getattr(ws, "cl_cap_rows", 0) != ws.cap_rows:
-            ws.cl_cap_rows = ws.cap_rows
-            if self.use_lstm:
-                H, R3 = self.lstm_units, ws.act[3].shape[0]
-                ws.zg = torch.zeros(R3 * 4 * H, **f32)
-                ws.cseq = torch.zeros(R3 * H, **f32)
-                ws.lstm_hseq = torch.zeros((R3 + 1, H), **f32)      # frame4's windows start one row on: one row behind the last
-            if self.attention is not None:
-                att, Rn = self.attention, ws.act[-1].shape[0]
-                ws.fa_x1 = torch.zeros((Rn, att.d_a), **f32)
-                ws.fa_F = torch.zeros((Rn, att.d_f), **f32)
-                ws.hw = torch.zeros_like(ws.act[-1])
+        bufs = super()._ragged_buffers_rows(cap)
+        if self.use_lstm:
+            H, R3 = self.lstm_units, bufs["act"][3].shape[0]
+            # lstm_hseq: frame4's windows start one row on, hence one row behind the last
+            bufs.update(zg=torch.zeros(R3 * 4 * H, **f32), cseq=torch.zeros(R3 * H, **f32), lstm_hseq=torch.zeros((R3 + 1, H), **f32))
+        if self.attention is not None:
+            att, last = self.attention, bufs["act"][-1]
+            bufs.update(fa_x1=torch.zeros((last.shape[0], att.d_a), **f32), fa_F=torch.zeros((last.shape[0], att.d_f), **f32),
+                        hw=torch.zeros_like(last))
+        return bufs
+
+    def _ragged_buffers_frames(self, cap):
+        """per input frame: the 2-D front-end's buffers (none without use_conv2d)"""
+        if not self.use_conv2d:
+            return {}
+        f32 = dict(dtype=torch.float32, device=self.device)
+        (_, F1, _), (_, F2, _) = self.fe_geom
+        C1, C2 = self.filters
+        return dict(cv_y=[torch.zeros((cap, F1, C1), **f32), torch.zeros((cap, F2, C2), **f32)], cv_a1=torch.zeros((cap, F1, C1), **f32),
+                    cv_out=torch.zeros((cap, C2), **f32), cv_c=[torch.zeros((4, C1), **f32), torch.zeros((4, C2), **f32)])
 
     def _ragged_conv2d(self, ws, X, dev_ro, B, total_T):
         """the 2-D front-end over all frames: both strided convolutions on each utterance's own rows
@@ -370,80 +381,46 @@ class CLSTM(SequentialTDNN):
                 nv.check(lib.lidbox_bn_relu_maxf_fwd(nv.ptr(y), 1, total_T, Fo, C, cp[2], cp[3], nv.ptr(ws.cv_out), total_T * C, st))
         return ws.cv_out
 
-    def forward_ragged(self, X, row_offsets, upto_embedding=False):
-        """SequentialTDNN.forward_ragged for every flag combination.  X [total_T, F] float32, contiguous, on the HIP device (F:
-        the model's input features); utterance b = rows row_offsets[b] .. row_offsets[b + 1].  use_conv2d: the front-end runs on
-        [total_T, ...] and its output is packed into level 0; use_lstm: level 3 carries a pad row before and after each
-        utterance's frames (ragged_plan's extra_pads), the LSTM runs there on lidbox_lstm_ragged_fwd and frame4 reads its h
-        sequence; use_attention: lidbox_freq_attention_fwd over the rows of the pooling level."""
-        from .ragged import ragged_plan, recurrent_plan
-        from .rnn_ragged import ragged_input
-        X, ro, lengths = ragged_input(X, row_offsets, self.model_input_dim)
-        B, n, total_T = len(lengths), len(self.convs), int(ro[-1])
-        with torch.cuda.device(self.device):
-            if B == 0:
-                D = self.denses[0].units if upto_embedding else self.denses[-1].units
-                return torch.zeros((0, D), dtype=torch.float32, device=self.device)
-            plan = ragged_plan(lengths, self.convs, {3: (1, 1)} if self.use_lstm else None)
-            ws = self.ragged_workspace(int(plan.off[-1]), B)
-            ws.B = B
-            self._ragged_extras(ws, total_T)
-            chans = [self.input_dim] + [c.filters for c in self.convs]
-            g, need = self.gemm, 16
-            for i, c in enumerate(self.convs):
-                need = max(need, g.rows_workspace(plan.rows[i + 1] - plan.pads[i + 1], c.filters, c.k * chans[i]))
-            H = self.lstm_units
-            if self.use_lstm:
-                need = max(need, g.rows_workspace(plan.rows[3], 4 * H, chans[3]))
-            att, Rn = self.attention, plan.rows[n]
-            if att is not None:
-                need = max(need, g.rows_workspace(Rn, att.d_a, chans[n]), g.rows_workspace(Rn, att.d_f, att.d_a))
-            din = ws.pooled.shape[1]
-            for d in self.denses:
-                need = max(need, self.dense_gemm.rows_workspace(B, d.units, din))
-                din = d.units
-            ws.reserve_gemm_ws(self, need)
-            # one upload: the segment offsets of every level, the source offsets, the pooling lengths, the LSTM's slot table
-            host = [plan.seg_offsets(i) for i in range(n + 1)] + [ro, plan.T[n]]
-            if self.use_lstm:
-                rp = recurrent_plan(plan.T[3])
-                host.append(np.stack([plan.seg_offsets(3)[:-1][rp.order], rp.sorted_lengths, rp.order]).reshape(-1))
-            dev = torch.from_numpy(np.concatenate(host).astype(np.int64)).to(self.device)
-            seg = [ctypes.c_void_p(dev.data_ptr() + 8 * i * (B + 1)) for i in range(n + 3)]
-            slots = ctypes.c_void_p(dev.data_ptr() + 8 * ((n + 2) * (B + 1) + B))
-            st, lib = nv.current_stream(), nv.lib
-            src = self._ragged_conv2d(ws, X, seg[n + 1], B, total_T) if self.use_conv2d else X
-            nv.check(lib.lidbox_ragged_pack_rows(nv.ptr(src), seg[n + 1], nv.ptr(ws.act[0]), seg[0], B, chans[0], plan.pads[0],
-                                                 self.convs[0].k - 1, st))
-            gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
-            for i, c in enumerate(self.convs):
-                M, p, Co, Ci = plan.rows[i + 1] - plan.pads[i + 1], plan.pads[i + 1], c.filters, chans[i]
-                A = _rows(ws.act[i].data_ptr(), 0, c.s * Ci, 1, M)
-                if i == 3 and self.use_lstm:
-                    # the LSTM on level 3 in place: one projection over all its rows, the walk over each utterance's own frames
-                    # (segment b: a pad row, its frames, a pad row at least), then frame4 on the h sequence, one row on
-                    R3 = plan.rows[3]
-                    nv.check(g.nn(_rows(ws.act[3].data_ptr(), 0, Ci, 1, R3), self._p("lstm.W"), 4 * H,
-                                  _rows(ws.zg.data_ptr(), 0, 4 * H, 1, R3), Ci, 4 * H, nv.EPI_BIAS, self._p("lstm.b"), gws, gws_n, st))
-                    nv.check(lib.lidbox_lstm_ragged_fwd(self._p("lstm.U"), None, 1, B, H, R3, slots,
-                                                        ctypes.c_void_p(rp.sorted_lengths.ctypes.data), nv.ptr(ws.zg),
-                                                        nv.ptr(ws.lstm_hseq), H, nv.ptr(ws.cseq), None, st))
-                    A = _rows(ws.lstm_hseq.data_ptr() + 4 * plan.lead[3] * H, 0, c.s * H, 1, M)
-                nv.check(g.nn(A, self._p(c.name + ".W"), Co, _rows(ws.act[i + 1].data_ptr() + 4 * p * Co, 0, Co, 1, M), c.k * Ci, Co,
-                              nv.EPI_BIAS_RELU if c.relu else nv.EPI_BIAS, self._p(c.name + ".b"), gws, gws_n, st))
-                if p > 0:
-                    nv.check(lib.lidbox_ragged_zero_rows(nv.ptr(ws.act[i + 1]), seg[i + 1], B, Co, p, st))
-            last, C = ws.act[n], chans[n]
-            if att is not None:
-                nv.check(g.nn(_rows(last.data_ptr(), 0, C, 1, Rn), self._p("Wf_1.W"), att.d_a,
-                              _rows(ws.fa_x1.data_ptr(), 0, att.d_a, 1, Rn), C, att.d_a, nv.EPI_RELU, None, gws, gws_n, st))
-                nv.check(g.nn(_rows(ws.fa_x1.data_ptr(), 0, att.d_a, 1, Rn), self._p("Wf_2.W"), att.d_f,
-                              _rows(ws.fa_F.data_ptr(), 0, att.d_f, 1, Rn), att.d_a, att.d_f, nv.EPI_NONE, None, gws, gws_n, st))
-                nv.check(lib.lidbox_freq_attention_fwd(nv.ptr(last), nv.ptr(ws.fa_F), Rn, C, att.d_f, nv.ptr(ws.fa_F), nv.ptr(ws.hw), st))
-                last = ws.hw
-            fn = lib.lidbox_stats_pool_ragged_fwd if self.pool == "stats" else lib.lidbox_avg_pool_ragged_fwd
-            nv.check(fn(nv.ptr(last), C, seg[n], seg[n + 2], B, C, nv.ptr(ws.pooled), st))
-            return self._forward_head(ws, upto_embedding)[:B]
+    def _ragged_pass(self, ws, plan, X, ro, upto_embedding):
+        """SequentialTDNN's ragged pass for every flag combination, built from its helpers.  X [total_T, F] (F: the model's
+        input features).  use_conv2d: the front-end runs on [total_T, ...] and its output is packed into level 0; use_lstm: the
+        LSTM runs on level 3 (its pad rows: `_ragged_plan`) on lidbox_lstm_ragged_fwd and frame4 reads its h sequence;
+        use_attention: lidbox_freq_attention_fwd over the rows of the pooling level."""
+        st, lib, g = nv.current_stream(), nv.lib, self.gemm
+        B, n, H, att = plan.B, len(self.convs), self.lstm_units, self.attention
+        R3, C3, Rn, Cn = plan.rows[3], ws.act[3].shape[1], plan.rows[n], ws.act[n].shape[1]
+        need = self._ragged_gemm_need(ws, plan)
+        if self.use_lstm:
+            need = max(need, g.rows_workspace(R3, 4 * H, C3))
+        if att is not None:
+            need = max(need, g.rows_workspace(Rn, att.d_a, Cn), g.rows_workspace(Rn, att.d_f, att.d_a))
+        ws.reserve_gemm_ws(self, need)
+        gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
+        # the LSTM's walk over the segments of level 3; its slot table goes behind SequentialTDNN's in the one upload
+        rp = recurrent_plan(plan.T[3], plan.seg_offsets(3)) if self.use_lstm else None
+        table, seg = self._ragged_upload(plan, ro, [rp.slots()] if rp else [])
+        self._ragged_pack(ws, plan, seg, self._ragged_conv2d(ws, X, seg[n + 1], B, int(ro[-1])) if self.use_conv2d else X)
+        for i in range(n):
+            A = None
+            if i == 3 and rp:
+                # the LSTM on level 3 in place: one projection over all its rows, the walk over each utterance's own frames
+                # (segment b: a pad row, its frames, a pad row at least), then frame4 on the h sequence, one row on
+                nv.check(g.nn(_rows(ws.act[3].data_ptr(), 0, C3, 1, R3), self._p("lstm.W"), 4 * H,
+                              _rows(ws.zg.data_ptr(), 0, 4 * H, 1, R3), C3, 4 * H, nv.EPI_BIAS, self._p("lstm.b"), gws, gws_n, st))
+                nv.check(lib.lidbox_lstm_ragged_fwd(self._p("lstm.U"), None, 1, B, H, R3, seg[n + 3],
+                                                    ctypes.c_void_p(rp.sorted_lengths.ctypes.data), nv.ptr(ws.zg),
+                                                    nv.ptr(ws.lstm_hseq), H, nv.ptr(ws.cseq), None, st))
+                A = _rows(ws.lstm_hseq.data_ptr() + 4 * plan.lead[3] * H, 0, self.convs[3].s * H, 1, plan.rows[4] - plan.pads[4])
+            self._ragged_conv(ws, plan, seg, i, A)
+        last = ws.act[n]
+        if att is not None:
+            nv.check(g.nn(_rows(last.data_ptr(), 0, Cn, 1, Rn), self._p("Wf_1.W"), att.d_a,
+                          _rows(ws.fa_x1.data_ptr(), 0, att.d_a, 1, Rn), Cn, att.d_a, nv.EPI_RELU, None, gws, gws_n, st))
+            nv.check(g.nn(_rows(ws.fa_x1.data_ptr(), 0, att.d_a, 1, Rn), self._p("Wf_2.W"), att.d_f,
+                          _rows(ws.fa_F.data_ptr(), 0, att.d_f, 1, Rn), att.d_a, att.d_f, nv.EPI_NONE, None, gws, gws_n, st))
+            nv.check(lib.lidbox_freq_attention_fwd(nv.ptr(last), nv.ptr(ws.fa_F), Rn, Cn, att.d_f, nv.ptr(ws.fa_F), nv.ptr(ws.hw), st))
+            last = ws.hw
+        return self._ragged_pool_head(ws, plan, seg, upto_embedding, last)
 
     # ------------------------------------------------------------------ public call
     def _load_input(self, ws, x, training):

@@ -21,6 +21,9 @@ lambda * sum W^2 to the loss and 2 lambda W to the gradient (lidbox_l2_penalty).
 Parameter names: `conv_1.W`, `conv_1.b`, `conv_1_bn.gamma`, `blstm_forward.W`, `blstm_backward.U`, `output.W`; moving
 statistics `conv_1_bn.moving_mean`, ...  The BLSTM halves are named by the Bidirectional wrapper and the direction, because
 Keras numbers the inner `forward_lstm_N` per session.
+
+Ragged pass (inference, float32): `rnn_ragged.RaggedRecurrent` on `ragged_pass.RaggedPass`; the model adds its length check,
+its plan (per-level offsets and the BLSTM's `recurrent_plan`, with the capacity `rec` for the BLSTM's rows) and `_ragged_pass`.
 """
 import ctypes
 
@@ -31,7 +34,7 @@ from .. import _native as nv
 from .flat import BatchNormSpec, FlatModel, LSTMLayer, Workspace, _rows, lstm_layer_bwd, lstm_layer_fwd
 from .ragged import recurrent_plan
 from .rnn import LSTMSpec
-from .rnn_ragged import RaggedPlanOnDevice, RaggedRecurrent, RaggedRecurrentWorkspace
+from .rnn_ragged import RaggedPlanOnDevice, RaggedRecurrent
 from .tdnn import DenseSpec
 
 
@@ -77,20 +80,6 @@ def check_pooled_lengths(name, lengths, blocks):
         b = int(short[0])
         raise ValueError("%s: utterance %d has %d frames, which is too small for %d pooling layers (at least %d frames)"
                          % (name, b, int(lengths[b]), blocks, 2 ** blocks))
-
-
-class _RaggedWorkspace(RaggedRecurrentWorkspace):
-    """the ragged pass's buffers: per input row (the conv and pool outputs), per row of the BLSTM's layout (`cap_rec`) and per
-    utterance, each grown by capacity"""
-
-    def __init__(self, model):
-        super().__init__(model)
-        self.cap_rec = 0
-
-    def reserve_rec(self, model, rows):
-        if rows > self.cap_rec:
-            self.cap_rec = max(int(rows), self.cap_rec + self.cap_rec // 2)
-            self.__dict__.update(model._ragged_buffers_rec(self.cap_rec))
 
 
 class _Workspace(Workspace):
@@ -157,7 +146,6 @@ class ConvRecurrentModel(FlatModel, RaggedRecurrent):
     """Conv2D blocks -> Bidirectional(LSTM) final states -> Dense -> output activation (see the module docstring)."""
 
     workspace_class = _Workspace
-    ragged_workspace_class = _RaggedWorkspace
 
     def __init__(self, input_shape, convs2d, lstm_units, num_outputs, name="crnn", output_activation="softmax", seed=None,
                  device=None, compute_dtype="float32"):
@@ -290,7 +278,7 @@ class ConvRecurrentModel(FlatModel, RaggedRecurrent):
                 nv.check(lib.lidbox_conv2d_dgrad(nv.ptr(ws.dz), B, T, F, cin, C, self._p(l.name + ".W"), l.k, nv.ptr(ws.dp[i - 1]),
                                                  nv.ptr(ws.dgrad_ws), ws.dgrad_ws.numel(), st))
 
-    # ------------------------------------------------------------------ ragged pass (inference, float32; models/rnn_ragged.py)
+    # ------------------------------------------------------------ ragged pass (inference, float32; models/ragged_pass.py)
     def _ragged_embedding_dim(self):
         return 2 * self.lstm.units
 
@@ -310,62 +298,57 @@ class ConvRecurrentModel(FlatModel, RaggedRecurrent):
         return dict(x=torch.zeros((cap, D), **f32), zg=torch.zeros(2 * cap * 4 * H, **f32), cseq=torch.zeros(2 * cap * H, **f32),
                     hseq=torch.zeros((cap, 2 * H), **f32))
 
-    def _ragged_buffers_utts(self, cap):
+    def _ragged_buffers_B(self, cap):
         f32 = dict(dtype=torch.float32, device=self.device)
         return dict(hlast=torch.zeros((cap, 2 * self.lstm.units), **f32), h=[torch.zeros((cap, self.output_dim), **f32)],
                     logp=torch.zeros((cap, self.output_dim), **f32))
 
-    def forward_ragged(self, X, row_offsets, upto_embedding=False):
-        """Inference on utterances of different lengths in one pass.  X [total_T, F] float32, contiguous, on the HIP device;
-        utterance b = rows row_offsets[b] .. row_offsets[b + 1] (host array of B + 1 entries), each with at least
-        2^blocks frames.  Returns a view of the workspace: the model output [B, N] or, upto_embedding, the BLSTM's final states
-        [B, 2H] (the dense pass's stop_before_output) -- what the dense pass gives each utterance alone, up to the rounding of
-        another GEMM / LSTM path.  The blocks run over all frames at once (lidbox_conv2d_ragged_fwd ->
-        lidbox_bn_maxpool2d_ragged_fwd on per-level offsets T_b -> T_b // 2, utterances end to end); the last pool writes
-        into `recurrent_plan`'s layout over the T_b // 2^blocks, where the BLSTM is one projection GEMM per direction and
-        lidbox_lstm_ragged_fwd."""
-        X, ro, lengths = self._ragged_input(X, row_offsets)
-        B, n = len(lengths), len(self.convs2d)
-        check_pooled_lengths(self.name, lengths, n)
-        with torch.cuda.device(self.device):
-            if B == 0:
-                D = self._ragged_embedding_dim() if upto_embedding else self.output_dim
-                return torch.zeros((0, D), dtype=torch.float32, device=self.device)
-            st, lib = nv.current_stream(), nv.lib
-            offs = pooled_offsets(lengths, n)
-            plan = recurrent_plan(np.diff(offs[n]))
-            ws = self.ragged_workspace(int(ro[-1]), B)
-            ws.reserve_rec(self, plan.Rp)
-            ws.B = B
-            dev = RaggedPlanOnDevice(plan, ro, self.device, extra=offs[1:n])
-            dev_offs = [dev.ro] + dev.extra
-            Fs = [F for _, F in pooled_sizes(1, self.input_dim, n)]
-            x, cin = nv.ptr(X), 1
-            for i, l in enumerate(self.convs2d):
-                C, rows = l.filters, int(offs[i][-1])
-                nv.check(lib.lidbox_conv2d_ragged_fwd(x, dev_offs[i], B, rows, Fs[i], cin, self._p(l.name + ".W"), l.k, C,
-                                                      self._p(l.name + ".b"), 1, nv.ptr(ws.y), st))
-                cp = self._bn_fwd(l.bn_spec, None, 0, C, ws.c[i], None, ws, False, False)
-                if i + 1 < n:
-                    out, out_offs, out_rows = nv.ptr(ws.p[i]), dev_offs[i + 1], int(offs[i + 1][-1])
-                else:
-                    # the frames of utterance b go behind the pad row that opens its segment: y one row on, segments as they are
-                    out = ctypes.c_void_p(ws.x.data_ptr() + 4 * self.lstm_input_dim)
-                    out_offs, out_rows = dev.seg, plan.Rp - 1
-                nv.check(lib.lidbox_bn_maxpool2d_ragged_fwd(nv.ptr(ws.y), dev_offs[i], B, Fs[i], C, cp[2], cp[3], out, out_offs,
-                                                            out_rows, None, st))
-                x, cin = out, C
-            H, D = self.lstm.units, self.lstm_input_dim
-            self._ragged_lstm_layer(ws, plan, dev, _rows(ws.x.data_ptr(), 0, D, 1, plan.Rp), D, self.lstm.prefixes, H,
-                                    ws.hseq.data_ptr(), 2 * H, ws.hlast)
-            if upto_embedding:
-                return ws.hlast[:B]
-            N = self.output_dim
-            ws.reserve_gemm_ws(self, max(16, lib.lidbox_gemm_rows_workspace(B, N, 2 * H)))
-            nv.check(lib.lidbox_gemm_nn(_rows(ws.hlast.data_ptr(), 0, 2 * H, 1, B), self._p("output.W"), N,
-                                        _rows(ws.h[0].data_ptr(), 0, N, 1, B), 2 * H, N, nv.EPI_BIAS, self._p("output.b"),
-                                        nv.ptr(ws.gemm_ws), ws.gemm_ws.numel(), st))
-            return self._output_activation(ws, ws.h[0], N)[:B]
+    def _ragged_check_lengths(self, lengths):
+        check_pooled_lengths(self.name, lengths, len(self.convs2d))
+
+    def _ragged_plan(self, ro, lengths):
+        """(the offsets of every pooled level, the BLSTM's plan over the lengths behind the last pool)"""
+        offs = pooled_offsets(lengths, len(self.convs2d))
+        plan = recurrent_plan(np.diff(offs[-1]))
+        return (offs, plan), dict(rows=int(ro[-1]), B=plan.B, rec=plan.Rp)
+
+    def _ragged_pass(self, ws, plan, X, ro, upto_embedding):
+        """X [total_T, F], every utterance with at least 2^blocks frames; returns the model output [B, N] or, upto_embedding,
+        the BLSTM's final states [B, 2H] (the dense pass's stop_before_output).  The blocks run over all frames at once
+        (lidbox_conv2d_ragged_fwd -> lidbox_bn_maxpool2d_ragged_fwd on per-level offsets T_b -> T_b // 2, utterances end to
+        end); the last pool writes into `recurrent_plan`'s layout over the T_b // 2^blocks, where the BLSTM is one projection
+        GEMM per direction and lidbox_lstm_ragged_fwd."""
+        (offs, plan), B, n = plan, ws.B, len(self.convs2d)
+        st, lib = nv.current_stream(), nv.lib
+        dev = RaggedPlanOnDevice(plan, ro, self.device, extra=offs[1:n])
+        dev_offs = [dev.ro] + dev.extra
+        Fs = [F for _, F in pooled_sizes(1, self.input_dim, n)]
+        x, cin = nv.ptr(X), 1
+        for i, l in enumerate(self.convs2d):
+            C, rows = l.filters, int(offs[i][-1])
+            nv.check(lib.lidbox_conv2d_ragged_fwd(x, dev_offs[i], B, rows, Fs[i], cin, self._p(l.name + ".W"), l.k, C,
+                                                  self._p(l.name + ".b"), 1, nv.ptr(ws.y), st))
+            cp = self._bn_fwd(l.bn_spec, None, 0, C, ws.c[i], None, ws, False, False)
+            if i + 1 < n:
+                out, out_offs, out_rows = nv.ptr(ws.p[i]), dev_offs[i + 1], int(offs[i + 1][-1])
+            else:
+                # the frames of utterance b go behind the pad row that opens its segment: y one row on, segments as they are
+                out = ctypes.c_void_p(ws.x.data_ptr() + 4 * self.lstm_input_dim)
+                out_offs, out_rows = dev.seg, plan.Rp - 1
+            nv.check(lib.lidbox_bn_maxpool2d_ragged_fwd(nv.ptr(ws.y), dev_offs[i], B, Fs[i], C, cp[2], cp[3], out, out_offs,
+                                                        out_rows, None, st))
+            x, cin = out, C
+        H, D = self.lstm.units, self.lstm_input_dim
+        self._ragged_lstm_layer(ws, plan, dev, _rows(ws.x.data_ptr(), 0, D, 1, plan.Rp), D, self.lstm.prefixes, H,
+                                ws.hseq.data_ptr(), 2 * H, ws.hlast)
+        if upto_embedding:
+            return ws.hlast
+        N = self.output_dim
+        ws.reserve_gemm_ws(self, max(16, lib.lidbox_gemm_rows_workspace(B, N, 2 * H)))
+        nv.check(lib.lidbox_gemm_nn(_rows(ws.hlast.data_ptr(), 0, 2 * H, 1, B), self._p("output.W"), N,
+                                    _rows(ws.h[0].data_ptr(), 0, N, 1, B), 2 * H, N, nv.EPI_BIAS, self._p("output.b"),
+                                    nv.ptr(ws.gemm_ws), ws.gemm_ws.numel(), st))
+        return self._output_activation(ws, ws.h[0], N)
 
 
 __all__ = ["Conv2DSpec", "ConvRecurrentModel", "pooled_sizes", "pooled_lengths", "pooled_offsets"]

@@ -283,7 +283,7 @@ class GRUModel(FlatModel, RaggedRecurrent):
         return dict(x=torch.zeros((cap, self.input_dim), **f32), zg=torch.zeros(dirs * cap * 3 * H, **f32),
                     qh=torch.zeros(dirs * cap * H, **f32), hseq=[torch.zeros((cap, l.out_dim), **f32) for l in self.grus])
 
-    def _ragged_buffers_utts(self, cap):
+    def _ragged_buffers_B(self, cap):
         """what _forward_head reads of a workspace, for `cap` utterances"""
         f32 = dict(dtype=torch.float32, device=self.device)
         D = self.grus[-1].out_dim

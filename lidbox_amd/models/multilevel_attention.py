@@ -24,6 +24,8 @@ step is `dropout_step`, which the Trainer points at its optimizer step counter (
 
 Parameters carry the Keras names of the inner layers (`dense_block1_fc.W`, `dense_block2_bn.gamma`, `attention1_input.b`,
 `outputs.W`).
+
+Ragged pass (inference): `ragged_pass.RaggedPass` with `_ragged_pass`, which needs no layout of its own.
 """
 import ctypes
 
@@ -32,7 +34,7 @@ import torch
 from .. import _native as nv
 from .flat import FlatModel, Workspace, _rows
 from .gru_rnn import BatchNormSpec
-from .rnn_ragged import ragged_input
+from .ragged_pass import EmbeddingExtractor, RaggedPass, upload_int64
 from .tdnn import DenseSpec
 
 MAX_OUTPUTS = 1024          # lidbox_mla_attention_*: a row of class logits lives in the registers of one wave
@@ -78,38 +80,7 @@ class _Workspace(Workspace):
         self.pending = []
 
 
-class _RaggedWorkspace:
-    """Device buffers of the ragged inference pass, sized by capacity: `cap_rows` frames and `cap_B` utterances; a pass with
-    fewer of either uses the front of every buffer.  Inference keeps nothing for a backward pass, so one `a`, one `y` and one
-    `z` serve every level: level l's y overwrites level l - 1's once a_l = y_{l-1} W has been formed."""
-
-    def __init__(self, model):
-        self.cap_rows = self.cap_B = self.B = 0
-        f32 = dict(dtype=torch.float32, device=model.device)
-        self.consts = [torch.zeros((4, model.units), **f32) for _ in range(model.levels)]     # mean, invstd, scale, shift
-        self.gemm_ws = torch.empty(16, dtype=torch.uint8, device=model.device)
-
-    def reserve(self, model, rows, B):
-        """a capacity that is exceeded becomes at least half as large again; only its own buffers are replaced"""
-        f32 = dict(dtype=torch.float32, device=model.device)
-        H, K, L = model.units, model.output_dim, model.levels
-        if rows > self.cap_rows:
-            self.cap_rows = max(int(rows), self.cap_rows + self.cap_rows // 2)
-            self.a = torch.zeros((self.cap_rows, H), **f32)          # dense_block{l}_fc's output: the BatchNormalization input
-            self.y = torch.zeros((self.cap_rows, H), **f32)          # the block's output y_l
-            self.z = torch.zeros((self.cap_rows, K), **f32)          # attention logits
-        if B > self.cap_B:
-            self.cap_B = max(int(B), self.cap_B + self.cap_B // 2)
-            self.att = torch.zeros((self.cap_B, L * K), **f32)       # the concatenated attention outputs
-            self.h = torch.zeros((self.cap_B, K), **f32)             # logits
-            self.logp = torch.zeros((self.cap_B, K), **f32)
-
-    def reserve_gemm_ws(self, model, nbytes):
-        if nbytes > self.gemm_ws.numel():
-            self.gemm_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=model.device)
-
-
-class MultilevelAttentionModel(FlatModel):
+class MultilevelAttentionModel(FlatModel, RaggedPass):
     """L x (Dense -> BatchNormalization -> ReLU -> Dropout, with an attention pooling of its output) -> Concatenate -> Dense
     (see the module docstring)."""
 
@@ -204,68 +175,63 @@ class MultilevelAttentionModel(FlatModel):
             self._load_input(ws, x, False)
             return self.forward_ws(ws, training=False, stop_before_output=True).clone()
 
-    # ------------------------------------------------------------------ ragged pass (inference)
-    def ragged_refusal(self):
-        """why this model has no ragged pass (None: it has one; the model computes in float32 by construction)"""
-        return None
+    # ------------------------------------------------------------------ ragged pass (inference; models/ragged_pass.py)
+    def _ragged_embedding_dim(self):
+        return self.levels * self.output_dim
 
-    def ragged_workspace(self, rows, B):
-        """the model's one _RaggedWorkspace, with room for `rows` frames and B utterances"""
-        ws = getattr(self, "_rws", None)
-        if ws is None:
-            ws = self._rws = _RaggedWorkspace(self)
-        ws.reserve(self, rows, B)
-        return ws
+    def _ragged_plan(self, ro, lengths):
+        """no layout of its own: the frames stay where the caller has them"""
+        return None, dict(rows=int(ro[-1]), B=len(lengths))
 
-    def forward_ragged(self, X, row_offsets, upto_embedding=False):
-        """Inference on utterances of different lengths in one pass.  X [total_T, D] float32, contiguous, on the HIP device;
-        utterance b = rows row_offsets[b] .. row_offsets[b + 1] (host array of B + 1 entries: the conventions of
-        SequentialTDNN.forward_ragged).  Every layer in front of the pooling works on single frames, so X is the GEMM operand as
-        it stands; only the attention pooling knows the utterances (lidbox_mla_attention_ragged_fwd).  BatchNormalization
-        uses the moving statistics and the Dropout is off.  Returns a view of the workspace: the model output [B, K] or,
-        upto_embedding, the concatenated attention outputs [B, L*K] -- what the dense pass gives each utterance alone, up
-        to the rounding of another GEMM path.  The one upload is row_offsets."""
-        X, ro, lengths = ragged_input(X, row_offsets, self.input_dim)
-        B, R = len(lengths), int(X.shape[0])
+    def _ragged_buffers_rows(self, cap):
+        """per frame.  Inference keeps nothing for a backward pass, so one `a`, one `y` and one `z` serve every level: level
+        l's y overwrites level l - 1's once a_l = y_{l-1} W has been formed.  consts: every pass writes the scale and shift
+        it reads (`_bn_fwd`), so they may be replaced with the rest"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        H, K = self.units, self.output_dim
+        return dict(a=torch.zeros((cap, H), **f32),          # dense_block{l}_fc's output: the BatchNormalization input
+                    y=torch.zeros((cap, H), **f32),          # the block's output y_l
+                    z=torch.zeros((cap, K), **f32),          # attention logits
+                    consts=[torch.zeros((4, H), **f32) for _ in range(self.levels)])     # mean, invstd, scale, shift
+
+    def _ragged_buffers_B(self, cap):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        K = self.output_dim
+        return dict(att=torch.zeros((cap, self.levels * K), **f32),       # the concatenated attention outputs
+                    h=torch.zeros((cap, K), **f32), logp=torch.zeros((cap, K), **f32))
+
+    def _ragged_pass(self, ws, plan, X, ro, upto_embedding):
+        """X [total_T, D].  Every layer in front of the pooling works on single frames, so X is the GEMM operand as it stands;
+        only the attention pooling knows the utterances (lidbox_mla_attention_ragged_fwd).  BatchNormalization uses the
+        moving statistics and the Dropout is off.  Returns the model output [B, K] or, upto_embedding, the concatenated
+        attention outputs [B, L*K].  The one upload is row_offsets."""
+        B, R = ws.B, int(X.shape[0])
         H, K, L = self.units, self.output_dim, self.levels
-        with torch.cuda.device(self.device):
-            if B == 0:
-                return torch.zeros((0, L * K if upto_embedding else K), dtype=torch.float32, device=self.device)
-            st, lib = nv.current_stream(), nv.lib
-            ws = self.ragged_workspace(R, B)
-            ws.B = B
-            need, cin = max(lib.lidbox_gemm_rows_workspace(B, K, L * K), 16), self.input_dim
-            for _ in range(L):
-                need = max(need, lib.lidbox_gemm_rows_workspace(R, H, cin), lib.lidbox_gemm_rows_workspace(R, K, H))
-                cin = H
-            ws.reserve_gemm_ws(self, need)
-            gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
-            ro_dev = torch.from_numpy(ro).to(self.device)
-            a, y, z = (_rows(t.data_ptr(), 0, t.shape[1], 1, R) for t in (ws.a, ws.y, ws.z))
-            rows_in, cin = _rows(X.data_ptr(), 0, self.input_dim, 1, R), self.input_dim
-            for l in range(L):
-                fc, bn, at = self.blocks[l] + "_fc", self.bns[l], self.attentions[l]
-                nv.check(lib.lidbox_gemm_nn(rows_in, self._p(fc + ".W"), H, a, cin, H, nv.EPI_BIAS, self._p(fc + ".b"), gws, gws_n, st))
-                cp = self._bn_fwd(bn, ws.a, R, H, ws.consts[l], None, ws, False, False)
-                nv.check(lib.lidbox_bn_relu_dropout_fwd(nv.ptr(ws.a), R, H, cp[2], cp[3], 0.0, self.level_dropout_seed(l), None,
-                                                        nv.ptr(ws.y), st))
-                nv.check(lib.lidbox_gemm_nn(y, self._p(at + ".W"), K, z, H, K, nv.EPI_BIAS, self._p(at + ".b"), gws, gws_n, st))
-                nv.check(lib.lidbox_mla_attention_ragged_fwd(nv.ptr(ws.z), nv.ptr(ro_dev), B, K,
-                                                             ctypes.c_void_p(ws.att.data_ptr() + 4 * l * K), L * K, None, st))
-                rows_in, cin = y, H
-            if upto_embedding:
-                return ws.att[:B]
-            nv.check(lib.lidbox_gemm_nn(_rows(ws.att.data_ptr(), 0, L * K, 1, B), self._p("outputs.W"), K,
-                                        _rows(ws.h.data_ptr(), 0, K, 1, B), L * K, K, nv.EPI_BIAS, self._p("outputs.b"), gws, gws_n, st))
-            return self._output_activation(ws, ws.h, K)[:B]
-
-    def predict_ragged(self, X, row_offsets):
-        """the model output [B, K] of B utterances of different lengths (a fresh tensor)"""
-        return self.forward_ragged(X, row_offsets).clone()
-
-    def embed_ragged(self, X, row_offsets):
-        """the concatenated attention outputs [B, L*K] of B utterances of different lengths (a fresh tensor)"""
-        return self.forward_ragged(X, row_offsets, upto_embedding=True).clone()
+        st, lib = nv.current_stream(), nv.lib
+        need, cin = max(lib.lidbox_gemm_rows_workspace(B, K, L * K), 16), self.input_dim
+        for _ in range(L):
+            need = max(need, lib.lidbox_gemm_rows_workspace(R, H, cin), lib.lidbox_gemm_rows_workspace(R, K, H))
+            cin = H
+        ws.reserve_gemm_ws(self, need)
+        gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
+        table, (ro_dev,) = upload_int64([ro], self.device)
+        a, y, z = (_rows(t.data_ptr(), 0, t.shape[1], 1, R) for t in (ws.a, ws.y, ws.z))
+        rows_in, cin = _rows(X.data_ptr(), 0, self.input_dim, 1, R), self.input_dim
+        for l in range(L):
+            fc, bn, at = self.blocks[l] + "_fc", self.bns[l], self.attentions[l]
+            nv.check(lib.lidbox_gemm_nn(rows_in, self._p(fc + ".W"), H, a, cin, H, nv.EPI_BIAS, self._p(fc + ".b"), gws, gws_n, st))
+            cp = self._bn_fwd(bn, ws.a, R, H, ws.consts[l], None, ws, False, False)
+            nv.check(lib.lidbox_bn_relu_dropout_fwd(nv.ptr(ws.a), R, H, cp[2], cp[3], 0.0, self.level_dropout_seed(l), None,
+                                                    nv.ptr(ws.y), st))
+            nv.check(lib.lidbox_gemm_nn(y, self._p(at + ".W"), K, z, H, K, nv.EPI_BIAS, self._p(at + ".b"), gws, gws_n, st))
+            nv.check(lib.lidbox_mla_attention_ragged_fwd(nv.ptr(ws.z), ro_dev, B, K,
+                                                         ctypes.c_void_p(ws.att.data_ptr() + 4 * l * K), L * K, None, st))
+            rows_in, cin = y, H
+        if upto_embedding:
+            return ws.att
+        nv.check(lib.lidbox_gemm_nn(_rows(ws.att.data_ptr(), 0, L * K, 1, B), self._p("outputs.W"), K,
+                                    _rows(ws.h.data_ptr(), 0, K, 1, B), L * K, K, nv.EPI_BIAS, self._p("outputs.b"), gws, gws_n, st))
+        return self._output_activation(ws, ws.h, K)
 
     # ------------------------------------------------------------------ backward
     def backward_head_ws(self, ws):
@@ -327,25 +293,10 @@ def create(input_shape, num_outputs, output_activation="log_softmax", L=2, H=512
 loader = create      # lidbox/models/keras_utils.py:134 calls `model_module.loader(...)`
 
 
-class EmbeddingExtractor:
+def as_embedding_extractor(model):
     """The concatenated attention outputs [B, L*K] (the input of the `outputs` layer) in inference mode.  The reference has
     no as_embedding_extractor for this model (lidbox/models/multilevel_attention.py defines `create` alone); this one follows
     the other models' convention of cutting in front of the classification layer."""
-
-    def __init__(self, model):
-        self.model = model
-
-    def __call__(self, x, training=False):
-        return self.model.embed(x)
-
-    predict = __call__
-
-    def ragged(self, X, row_offsets):
-        """the embeddings [B, L*K] of B utterances of different lengths (MultilevelAttentionModel.embed_ragged)"""
-        return self.model.embed_ragged(X, row_offsets)
-
-
-def as_embedding_extractor(model):
     return EmbeddingExtractor(model)
 
 

@@ -1,6 +1,7 @@
 """
 Host plan of the ragged model pass: where utterances of DIFFERENT lengths live when a causal Conv1D stack runs over all of them in one
-GEMM per layer (no reference counterpart: tf.data batches need one shape).  Pure Python on host integers.
+GEMM per layer (no reference counterpart: tf.data batches need one shape).  Pure Python on host integers; what the models do with a
+plan -- the checks, the workspace, the one upload, the public calls -- is models/ragged_pass.py's.
 
 Conv i (i = 0 .. n-1) has kernel k_i and stride s_i, padding "causal", no dilation.  Level i is the input of conv i, level n the
 pooling input.  With
@@ -97,13 +98,15 @@ class RecurrentPlan:
         return np.ascontiguousarray(np.stack([self.seg[:-1][self.order], self.sorted_lengths, self.order]))
 
 
-def recurrent_plan(lengths):
-    """lengths: frames per utterance (each >= 1, ValueError otherwise).  Returns a RecurrentPlan."""
+def recurrent_plan(lengths, seg=None):
+    """lengths: frames per utterance (each >= 1, ValueError otherwise).  Returns a RecurrentPlan.  seg [B + 1]: the segments of
+    a caller whose [pad, frames, pad at least] segments lie elsewhere (clstm: level 3 of its `ragged_plan`); default: end to end."""
     T = np.asarray(lengths, np.int64).reshape(-1)
     if (T < 1).any():
         raise ValueError("every utterance needs at least one frame, got lengths %s" % T[T < 1][:8].tolist())
     B = len(T)
-    seg = np.concatenate(([0], np.cumsum(T))).astype(np.int64) + 2 * np.arange(B + 1, dtype=np.int64)
+    if seg is None:
+        seg = np.concatenate(([0], np.cumsum(T))).astype(np.int64) + 2 * np.arange(B + 1, dtype=np.int64)
     order = np.argsort(-T, kind="stable").astype(np.int64)
     sorted_lengths = np.ascontiguousarray(T[order])
     T_max = int(sorted_lengths[0]) if B else 0

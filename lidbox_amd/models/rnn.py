@@ -192,7 +192,7 @@ class RecurrentModel(FlatModel, RaggedRecurrent):
         return dict(x=torch.zeros((cap, self.input_dim), **f32), zg=torch.zeros(dirs * cap * 4 * H, **f32),
                     cseq=torch.zeros(dirs * cap * H, **f32), hseq=[torch.zeros((cap, l.out_dim), **f32) for l in self.lstms])
 
-    def _ragged_buffers_utts(self, cap):
+    def _ragged_buffers_B(self, cap):
         f32 = dict(dtype=torch.float32, device=self.device)
         if self.head == "avg_concat":
             h = [torch.zeros((cap, self.output_dim), **f32)]

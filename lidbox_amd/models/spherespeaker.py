@@ -27,6 +27,7 @@ import torch
 from .. import _native as nv
 from .flat import FlatModel, LSTMLayer, Workspace, _rows, lstm_layer_bwd, lstm_layer_fwd
 from .gru_rnn import BatchNormSpec
+from .ragged_pass import EmbeddingExtractor
 from .rnn_ragged import RaggedRecurrent
 from .tdnn import DenseSpec
 
@@ -191,7 +192,7 @@ class SphereSpeakerModel(FlatModel, RaggedRecurrent):
                     cseq=torch.zeros(2 * cap * H, **f32), hcat=torch.zeros((cap, C6), **f32), ycat=torch.zeros((cap, C6), **f32),
                     a=torch.zeros((cap, E), **f32), c_cat=torch.zeros((4, C6), **f32), c_pool=torch.zeros((4, E), **f32))
 
-    def _ragged_buffers_utts(self, cap):
+    def _ragged_buffers_B(self, cap):
         """what _forward_pooled reads of a workspace, for `cap` utterances"""
         f32 = dict(dtype=torch.float32, device=self.device)
         E, N = self.embedding_dim, self.output_dim
@@ -278,24 +279,9 @@ def create(input_shape, num_outputs, embedding_dim=1000, output_activation="log_
 loader = create      # lidbox/models/keras_utils.py:134 calls `model_module.loader(...)`
 
 
-class EmbeddingExtractor:
-    """reference spherespeaker.py:23-25: the output of the `l2_normalize` layer, in inference mode"""
-
-    def __init__(self, model):
-        self.model = model
-
-    def __call__(self, x, training=False):
-        return self.model.embed(x)
-
-    predict = __call__
-
-    def ragged(self, X, row_offsets):
-        """the embeddings [B, embedding_dim] of B utterances of different lengths (SphereSpeakerModel.embed_ragged)"""
-        return self.model.embed_ragged(X, row_offsets)
-
-
 def as_embedding_extractor(model):
+    """reference spherespeaker.py:23-25: the output of the `l2_normalize` layer, in inference mode, [B, embedding_dim]"""
     return EmbeddingExtractor(model)
 
 
-__all__ = ["SphereSpeakerModel", "create", "loader", "as_embedding_extractor"]
+__all__ = ["SphereSpeakerModel", "EmbeddingExtractor", "create", "loader", "as_embedding_extractor"]

@@ -16,6 +16,11 @@ HBM layout
     that READS it.  A causal window is then k*C_i contiguous floats (row stride s*C_i): Conv1D
     forward / wgrad are GEMMs over implicit rows and no im2col buffer exists.  Gradient buffers
     d_act[i] share the layout (the pad rows just absorb unused dgrad output).
+
+Ragged pass (inference, float32; utterances of different lengths in one pass): the public calls, the checks and the workspace
+are `ragged_pass.RaggedPass`'s, the layout `ragged.ragged_plan`'s.  `_ragged_pass` is the pass, written from the helpers
+`_ragged_gemm_need`, `_ragged_upload`, `_ragged_pack`, `_ragged_conv` and `_ragged_pool_head`, which models/clstm.py composes
+with its own layers.
 """
 import ctypes
 import os
@@ -26,6 +31,8 @@ import torch
 
 from .. import _native as nv
 from .flat import FlatParams, Workspace, _align4, _rows
+from .ragged import ragged_plan
+from .ragged_pass import EmbeddingExtractor, RaggedPass, upload_int64  # noqa: F401  (xvector, cnn import it here)
 
 
 class ConvSpec:
@@ -283,43 +290,7 @@ class _Workspace(Workspace):
         return self.act[0][:, self.pads[0]:, :]
 
 
-class _RaggedWorkspace:
-    """The device buffers of the ragged pass (models/ragged.py), sized by capacity: `cap_rows` top-level rows and `cap_B`
-    utterances.  act[i] is level i: cap_rows * cum_i rows of C_i floats plus the k_i - 1 rows the last GEMM rows read behind them.
-    Zero-initialised; a pass writes what it reads (lidbox_ragged_pack_rows every level-0 row, the GEMMs every row behind the first
-    pad, lidbox_ragged_zero_rows every pad), so rows left over from a larger earlier pass are never read by a valid output row."""
-
-    def __init__(self, model):
-        self.cap_rows = self.cap_B = self.B = 0
-        self.gemm_ws = torch.empty(16, dtype=torch.uint8, device=model.device)
-
-    def reserve(self, model, top_rows, B):
-        """room for top_rows top-level rows and B utterances: a capacity that is exceeded becomes at least half as large again
-        and only its own buffers are replaced (the level buffers for rows, the pooled / head buffers for utterances)"""
-        f32 = dict(dtype=torch.float32, device=model.device)
-        convs = model.convs
-        chans = [model.input_dim] + [c.filters for c in convs]
-        if top_rows > self.cap_rows:
-            self.cap_rows = max(int(top_rows), self.cap_rows + self.cap_rows // 2)
-            cum = [1] * len(chans)
-            for i in range(len(convs) - 1, -1, -1):
-                cum[i] = cum[i + 1] * convs[i].s
-            tails = [c.k - 1 for c in convs] + [0]
-            self.act = [torch.zeros((self.cap_rows * cum[i] + tails[i], chans[i]), **f32) for i in range(len(chans))]
-        if B > self.cap_B:
-            self.cap_B = max(int(B), self.cap_B + self.cap_B // 2)
-            P = 2 * chans[-1] if model.pool == "stats" else chans[-1]
-            self.pooled = torch.zeros((self.cap_B, P), **f32)
-            self.h = [torch.zeros((self.cap_B, d.units), **f32) for d in model.denses]
-            self.logp = torch.zeros((self.cap_B, model.denses[-1].units), **f32)
-            self.emb = torch.zeros((self.cap_B, model.denses[0].units), **f32)
-
-    def reserve_gemm_ws(self, model, nbytes):
-        if nbytes > self.gemm_ws.numel():
-            self.gemm_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=model.device)
-
-
-class SequentialTDNN(FlatParams):
+class SequentialTDNN(FlatParams, RaggedPass):
     """convs -> pool -> denses -> log_softmax, parameters in one flat buffer (accessors and workspace cache: models/flat.py)."""
 
     workspace_class = _Workspace
@@ -362,6 +333,7 @@ class SequentialTDNN(FlatParams):
         self.dropout_seed = int(np.random.default_rng(seed).integers(1, 2 ** 62))
         self._dropout_calls = 0
         self.embedding_layer = self.denses[0].name
+        self.output_dim = self.denses[-1].units
         # GEMM arithmetic: "float32" (exact fp32 MFMA) or "bfloat16" (operands rounded to bf16 on chip, fp32
         # accumulate; all buffers, the master weights and every non-GEMM kernel stay fp32)
         self.gemm = _GemmFamily(compute_dtype)
@@ -1178,7 +1150,7 @@ class SequentialTDNN(FlatParams):
 
     predict = __call__
 
-    # ------------------------------------------------------------------ ragged pass (inference, float32)
+    # ------------------------------------------------------------ ragged pass (inference, float32; models/ragged_pass.py)
     def ragged_refusal(self):
         """why this model has no ragged pass (None: it has one).  The layout of models/ragged.py is that of a plain causal,
         undilated Conv1D stack in front of the pooling."""
@@ -1195,88 +1167,87 @@ class SequentialTDNN(FlatParams):
             return "the ragged pass does not run the layers %s puts between its convolutions (_before_conv)" % type(self).__name__
         return None
 
-    def ragged_workspace(self, top_rows, B):
-        """the model's one _RaggedWorkspace, with room for top_rows top-level rows and B utterances (_RaggedWorkspace.reserve)"""
-        ws = getattr(self, "_rws", None)
-        if ws is None:
-            ws = self._rws = _RaggedWorkspace(self)
-        ws.reserve(self, top_rows, B)
-        return ws
+    def _ragged_embedding_dim(self):
+        return self.denses[0].units
 
-    def forward_ragged(self, X, row_offsets, upto_embedding=False):
-        """Inference on utterances of different lengths in one pass.  X [total_T, C] float32, contiguous, on the HIP device;
-        utterance b = rows row_offsets[b] .. row_offsets[b + 1] (host array of B + 1 entries: the conventions of
-        features.cmvn_ragged).  Returns a view of the workspace: the model output [B, num_outputs] or, upto_embedding, the
-        embedding [B, D] -- what the dense pass gives each utterance alone, up to the rounding of another GEMM / pooling path.
-        pack -> per conv one GEMM over all utterances (+ the pad-row repair) -> ragged pooling -> the dense head."""
-        reason = self.ragged_refusal()
-        if reason:
-            raise ValueError(reason)
-        X = nv.require_gpu_tensor(X, "X", torch.float32)
-        if X.dim() != 2 or X.shape[1] != self.input_dim or not X.is_contiguous():
-            raise ValueError("expected a contiguous input [total_T, %d], got %s" % (self.input_dim, tuple(X.shape)))
-        ro = np.ascontiguousarray(np.asarray(row_offsets, np.int64).reshape(-1))
-        if len(ro) < 1 or ro[0] != 0 or (np.diff(ro) < 0).any() or int(ro[-1]) != X.shape[0]:
-            raise ValueError("row_offsets must rise from 0 to the %d rows of X" % X.shape[0])
-        lengths = np.diff(ro)
-        if (lengths < 1).any():
-            raise ValueError("utterance %d has length 0: every utterance needs at least one frame" % int(np.flatnonzero(lengths < 1)[0]))
-        from .ragged import ragged_plan
-        B, n = len(lengths), len(self.convs)
-        with torch.cuda.device(self.device):
-            if B == 0:
-                D = self.denses[0].units if upto_embedding else self.denses[-1].units
-                return torch.zeros((0, D), dtype=torch.float32, device=self.device)
-            plan = ragged_plan(lengths, self.convs)
-            ws = self.ragged_workspace(int(plan.off[-1]), B)
-            ws.B = B
-            chans = [self.input_dim] + [c.filters for c in self.convs]
-            g, need = self.gemm, 16
-            for i, c in enumerate(self.convs):
-                need = max(need, g.rows_workspace(plan.rows[i + 1] - plan.pads[i + 1], c.filters, c.k * chans[i]))
-            din = ws.pooled.shape[1]
-            for d in self.denses:
-                need = max(need, self.dense_gemm.rows_workspace(B, d.units, din))
-                din = d.units
-            ws.reserve_gemm_ws(self, need)
-            # one upload: the segment offsets of every level, the source offsets, the pooling lengths
-            host = np.concatenate([plan.seg_offsets(i) for i in range(n + 1)] + [ro, plan.T[n]])
-            dev = torch.from_numpy(host).to(self.device)
-            seg = [ctypes.c_void_p(dev.data_ptr() + 8 * i * (B + 1)) for i in range(n + 3)]
-            st, lib = nv.current_stream(), nv.lib
-            k0 = self.convs[0].k if n else 1
-            nv.check(lib.lidbox_ragged_pack_rows(nv.ptr(X), seg[n + 1], nv.ptr(ws.act[0]), seg[0], B, chans[0], plan.pads[0], k0 - 1, st))
-            for i, c in enumerate(self.convs):
-                M, p, Co = plan.rows[i + 1] - plan.pads[i + 1], plan.pads[i + 1], c.filters
-                nv.check(g.nn(_rows(ws.act[i].data_ptr(), 0, c.s * chans[i], 1, M), self._p(c.name + ".W"), Co,
-                              _rows(ws.act[i + 1].data_ptr() + 4 * p * Co, 0, Co, 1, M), c.k * chans[i], Co,
+    def _ragged_plan(self, ro, lengths):
+        plan = ragged_plan(lengths, self.convs)
+        return plan, dict(rows=int(plan.off[-1]), B=plan.B)
+
+    def _ragged_buffers_rows(self, cap):
+        """per top-level row of models/ragged.py's layout: act[i] is level i, cap * cum_i rows of C_i floats plus the k_i - 1
+        rows the last GEMM rows read behind them.  Zero-initialised; a pass writes what it reads (lidbox_ragged_pack_rows every
+        level-0 row, the GEMMs every row behind the first pad, lidbox_ragged_zero_rows every pad), so rows left over from a
+        larger earlier pass are never read by a valid output row."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        chans = [self.input_dim] + [c.filters for c in self.convs]
+        cum = [1] * len(chans)
+        for i in range(len(self.convs) - 1, -1, -1):
+            cum[i] = cum[i + 1] * self.convs[i].s
+        tails = [c.k - 1 for c in self.convs] + [0]
+        return dict(act=[torch.zeros((cap * cum[i] + tails[i], chans[i]), **f32) for i in range(len(chans))])
+
+    def _ragged_buffers_B(self, cap):
+        """per utterance: the pooled rows and what _forward_head reads of a workspace"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        C = self.convs[-1].filters if self.convs else self.input_dim
+        return dict(pooled=torch.zeros((cap, 2 * C if self.pool == "stats" else C), **f32),
+                    h=[torch.zeros((cap, d.units), **f32) for d in self.denses],
+                    logp=torch.zeros((cap, self.denses[-1].units), **f32), emb=torch.zeros((cap, self.denses[0].units), **f32))
+
+    def _ragged_gemm_need(self, ws, plan):
+        """bytes of GEMM workspace of the convs over the plan's rows and of the dense head over its utterances"""
+        need = 16
+        for i, c in enumerate(self.convs):
+            need = max(need, self.gemm.rows_workspace(plan.rows[i + 1] - plan.pads[i + 1], c.filters, c.k * ws.act[i].shape[1]))
+        din = ws.pooled.shape[1]
+        for d in self.denses:
+            need = max(need, self.dense_gemm.rows_workspace(plan.B, d.units, din))
+            din = d.units
+        return need
+
+    def _ragged_upload(self, plan, ro, extra=()):
+        """one upload: the segment offsets of every level, the source offsets, the pooling lengths, then the caller's `extra`
+        int64 arrays.  Returns (the tensor, seg): seg[i] the offsets of level i <= n, seg[n + 1] the source's, seg[n + 2] the
+        lengths, seg[n + 3 ...] the extras"""
+        n = len(self.convs)
+        return upload_int64([plan.seg_offsets(i) for i in range(n + 1)] + [ro, plan.T[n]] + list(extra), self.device)
+
+    def _ragged_pack(self, ws, plan, seg, src):
+        """the rows of src [total_T, C_0] into level 0, every utterance behind its causal zero rows"""
+        k0 = self.convs[0].k if self.convs else 1
+        nv.check(nv.lib.lidbox_ragged_pack_rows(nv.ptr(src), seg[len(self.convs) + 1], nv.ptr(ws.act[0]), seg[0], plan.B,
+                                                ws.act[0].shape[1], plan.pads[0], k0 - 1, nv.current_stream()))
+
+    def _ragged_conv(self, ws, plan, seg, i, A=None):
+        """conv i as one GEMM over all utterances, level i -> level i + 1, then the pad-row repair: the GEMM also writes the
+        pad rows of utterances 1 .. B - 1, which are zeroed again.  A: the rows descriptor of another A operand than level i
+        (clstm: frame4 on its LSTM's h sequence)"""
+        c, st = self.convs[i], nv.current_stream()
+        M, p, Co, Ci = plan.rows[i + 1] - plan.pads[i + 1], plan.pads[i + 1], c.filters, ws.act[i].shape[1]
+        if A is None:
+            A = _rows(ws.act[i].data_ptr(), 0, c.s * Ci, 1, M)
+        nv.check(self.gemm.nn(A, self._p(c.name + ".W"), Co, _rows(ws.act[i + 1].data_ptr() + 4 * p * Co, 0, Co, 1, M), c.k * Ci, Co,
                               nv.EPI_BIAS_RELU if c.relu else nv.EPI_BIAS, self._p(c.name + ".b"),
                               nv.ptr(ws.gemm_ws), ws.gemm_ws.numel(), st))
-                if p > 0:
-                    nv.check(lib.lidbox_ragged_zero_rows(nv.ptr(ws.act[i + 1]), seg[i + 1], B, Co, p, st))
-            fn = lib.lidbox_stats_pool_ragged_fwd if self.pool == "stats" else lib.lidbox_avg_pool_ragged_fwd
-            nv.check(fn(nv.ptr(ws.act[n]), chans[n], seg[n], seg[n + 2], B, chans[n], nv.ptr(ws.pooled), st))
-            return self._forward_head(ws, upto_embedding)[:B]
+        if p > 0:
+            nv.check(nv.lib.lidbox_ragged_zero_rows(nv.ptr(ws.act[i + 1]), seg[i + 1], plan.B, Co, p, st))
 
-    def predict_ragged(self, X, row_offsets):
-        """log-probs (or what output_activation makes) [B, num_outputs] of B utterances of different lengths (a fresh tensor)"""
-        return self.forward_ragged(X, row_offsets).clone()
+    def _ragged_pool_head(self, ws, plan, seg, upto_embedding, last=None):
+        """ragged pooling of the top level (or of `last`, a buffer in its layout) into ws.pooled, then the dense head"""
+        n = len(self.convs)
+        last = ws.act[n] if last is None else last
+        C = last.shape[1]
+        fn = nv.lib.lidbox_stats_pool_ragged_fwd if self.pool == "stats" else nv.lib.lidbox_avg_pool_ragged_fwd
+        nv.check(fn(nv.ptr(last), C, seg[n], seg[n + 2], plan.B, C, nv.ptr(ws.pooled), nv.current_stream()))
+        return self._forward_head(ws, upto_embedding)
 
-    def embed_ragged(self, X, row_offsets):
-        """`embed` for B utterances of different lengths: [B, D] (a fresh tensor)"""
-        return self.forward_ragged(X, row_offsets, upto_embedding=True).clone()
-
-
-class EmbeddingExtractor:
-    """Result of `as_embedding_extractor(model)` (reference xvector.py:70-73 / cnn.py:19-22)."""
-
-    def __init__(self, model):
-        self.model = model
-        self.name = model.name + ":" + model.embedding_layer
-
-    def __call__(self, x, training=False):
-        return self.model.embed(x)
-
-    def ragged(self, X, row_offsets):
-        """the embeddings [B, D] of B utterances of different lengths (SequentialTDNN.embed_ragged)"""
-        return self.model.embed_ragged(X, row_offsets)
+    def _ragged_pass(self, ws, plan, X, ro, upto_embedding):
+        """X [total_T, C]; returns the model output [B, num_outputs] or, upto_embedding, the embedding [B, D] (`embed`):
+        pack -> per conv one GEMM over all utterances (+ the pad-row repair) -> ragged pooling -> the dense head."""
+        ws.reserve_gemm_ws(self, self._ragged_gemm_need(ws, plan))
+        table, seg = self._ragged_upload(plan, ro)
+        self._ragged_pack(ws, plan, seg, X)
+        for i in range(len(self.convs)):
+            self._ragged_conv(ws, plan, seg, i)
+        return self._ragged_pool_head(ws, plan, seg, upto_embedding)

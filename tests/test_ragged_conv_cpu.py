@@ -114,4 +114,5 @@ def test_symbols_in_header_and_ctypes_table():
     for cls in (ConvRecurrentModel, CLSTM):
         for attr in ("ragged_refusal", "forward_ragged", "predict_ragged", "embed_ragged"):
             assert callable(getattr(cls, attr)), (cls, attr)
-    assert CLSTM.forward_ragged is not SequentialTDNN.forward_ragged and CLSTM.ragged_refusal is not SequentialTDNN.ragged_refusal
+    # forward_ragged is the shared template (models/ragged_pass.py); `_ragged_pass` holds a model's own pass
+    assert CLSTM._ragged_pass is not SequentialTDNN._ragged_pass and CLSTM.ragged_refusal is not SequentialTDNN.ragged_refusal

@@ -416,6 +416,25 @@ def test_crnn_zero_padded_dense_batch_is_a_different_computation(F):
         assert (err[b] > CRNN_TOL) == (T < max(CRNN_LENGTHS)), (b, T, err[b])
 
 
+def test_crnn_workspace_grows_to_the_same_bits():
+    """a model whose first ragged call is small: the second, full call grows rows, BLSTM rows and utterances, and gives the
+    bits of the model that saw the full call first"""
+    from test_crnn_gpu import _small
+    F = 33
+    big, xs, X, off, out_ref, _ = _crnn_case(F)
+    m = _small(T=100, F=F)
+    m.set_weights(big.get_weights())
+    few = m.predict_ragged(X[off[1]:off[4]], off[1:5] - off[1]).cpu().numpy()
+    assert np.abs(few - out_ref[1:4]).max() <= CRNN_TOL
+    ws = m._rws
+    caps, old = (ws.cap_rows, ws.cap_rec, ws.cap_B), (ws.y, ws.x, ws.hlast)
+    out = m.predict_ragged(X, off).cpu().numpy()
+    assert np.abs(out - out_ref).max() <= CRNN_TOL
+    assert _same_bits(out, big.predict_ragged(X, off).cpu().numpy())
+    assert m._rws is ws and all(new > was for new, was in zip((ws.cap_rows, ws.cap_rec, ws.cap_B), caps)), caps
+    assert all(new.data_ptr() != was.data_ptr() for new, was in zip((ws.y, ws.x, ws.hlast), old))
+
+
 # ---------------------------------------------------------------------------------------------------- clstm
 CLSTM_LENGTHS = [1, 4, 20, 7, 6, 33, 2, 11]
 CLSTM_TOL = 3e-6
@@ -469,11 +488,46 @@ def test_clstm_ragged_matches_transcription_and_dense_per_utterance(flag, F):
     print("clstm %s F=%d ragged: predict vs float64 %.3g, vs dense %.3g; embed vs float64 %.3g, vs dense %.3g" % (flag, F, *e))
     assert max(e) <= CLSTM_TOL, e
     # a second, smaller call reuses the workspace
-    ws, caps = m._rws, (m._rws.cap_rows, m._rws.cap_B)
+    ws, caps = m._rws, (m._rws.cap_rows, m._rws.cap_frames, m._rws.cap_B)
     few = m.predict_ragged(X[off[2]:off[5]], off[2:6] - off[2]).cpu().numpy()
-    assert m._rws is ws and (ws.cap_rows, ws.cap_B) == caps
+    assert m._rws is ws and (ws.cap_rows, ws.cap_frames, ws.cap_B) == caps
     assert np.abs(few - out_ref[2:5]).max() <= CLSTM_TOL
     assert m.predict_ragged(X[:0], [0]).shape == (0, out_ref.shape[1])
+
+
+@pytest.mark.parametrize("flag", ["lstm", "attention", "all"])
+def test_clstm_workspace_grows_to_the_same_bits(flag):
+    """a model whose first ragged call is utterances 2..4: the second call, all eight, grows rows, frames and utterances; the
+    level buffers and the LSTM / attention buffers sized off them are replaced together; the result has the bits of the model
+    that saw the large call first"""
+    from test_clstm_gpu import FLAGS, _model
+    F = 20
+    big, xs, X, off, out_ref, _ = _clstm_case(flag, F)
+    m = _model(FLAGS[flag], 33, F, seed=F, **CLSTM_WIDTHS)
+    m.set_weights(big.get_weights())
+    few = m.predict_ragged(X[off[2]:off[5]], off[2:6] - off[2]).cpu().numpy()
+    assert np.abs(few - out_ref[2:5]).max() <= CLSTM_TOL
+    ws = m._rws
+    extras = [n for n, on in (("zg", m.use_lstm), ("cseq", m.use_lstm), ("lstm_hseq", m.use_lstm), ("fa_x1", m.use_attention),
+                              ("fa_F", m.use_attention), ("hw", m.use_attention)) if on]
+    caps, old = (ws.cap_rows, ws.cap_frames, ws.cap_B), [ws.act[3], ws.act[-1]] + [getattr(ws, n) for n in extras]
+    cv_out = getattr(ws, "cv_out", None)
+    out = m.predict_ragged(X, off).cpu().numpy()
+    assert np.abs(out - out_ref).max() <= CLSTM_TOL
+    assert _same_bits(out, big.predict_ragged(X, off).cpu().numpy())
+    assert m._rws is ws and all(new > was for new, was in zip((ws.cap_rows, ws.cap_frames, ws.cap_B), caps)), caps
+    # the old buffers are still referenced, so a new buffer cannot have an old one's address
+    new = [ws.act[3], ws.act[-1]] + [getattr(ws, n) for n in extras]
+    assert all(a.data_ptr() != b.data_ptr() for a, b in zip(new, old)), extras
+    H = m.lstm_units
+    if m.use_lstm:
+        R3 = ws.act[3].shape[0]
+        assert ws.zg.numel() == R3 * 4 * H and ws.cseq.numel() == R3 * H and tuple(ws.lstm_hseq.shape) == (R3 + 1, H)
+    if m.use_attention:
+        assert ws.hw.shape == ws.act[-1].shape and ws.fa_x1.shape[0] == ws.fa_F.shape[0] == ws.act[-1].shape[0]
+    if flag == "all":
+        assert ws.cv_out.data_ptr() != cv_out.data_ptr() and ws.cv_out.shape[0] == ws.cap_frames == int(off[-1]) > cv_out.shape[0]
+        assert all(t.shape[0] == ws.cap_frames for t in ws.cv_y + [ws.cv_a1])
 
 
 # ---------------------------------------------------------------------------------------------------- entry points, refusals
