@@ -263,7 +263,12 @@ size_t lidbox_gemm_rows_workspace(long M, int N, int K);
 
 /* C[M,N] = epi( A[M,K] . B )  -- forward of Conv1D/Dense (a12/a14), linear_to_mel (a4).
  * A: implicit rows (K contiguous).  B: [K,N] row-major, ldb (Keras kernel layout [k*C_in, C_out]).
- * C: implicit rows (N contiguous).  aux: bias[N] or mask (layout of C) or NULL. */
+ * C: implicit rows (N contiguous).  aux: bias[N] or mask (layout of C) or NULL.
+ * Extents (lidbox_gemm_nn, _nt, _tn and lidbox_gemm_nt_tn alike): any extent of A, B and C is legal.  The LDS-DMA and stream-K
+ * kernels address an operand with 32-bit byte offsets from one 64-bit base and are chosen while
+ * ((batch - 1) batch_stride + (rows_per_batch - 1) row_stride + cols + 64) * 4 < 4.0e9 for an implicit-rows operand and
+ * (rows of B + 16) * ldb * 4 < 4.0e9 for B (above 2^31: offsets with bit 31 set are in use); beyond, the register-staged kernels
+ * with 64-bit offsets run (lidbox_gemm_last_family() == 0).  No limit applies to C.  tests/test_gemm_far_gpu.py runs both sides. */
 int lidbox_gemm_nn(lidbox_rows_t A, const float* Bm, long ldb, lidbox_rows_out_t C,
                    int K, int N, int epilogue, const float* aux,
                    void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
@@ -372,7 +377,11 @@ int lidbox_gemm_bf16_tn(lidbox_rows_t A, lidbox_rows_t Bm, float* C, long ldc, i
  * Numerically identical to lidbox_gemm_bf16_nn/_nt on the fp32 originals (rounding happens where the shadow is
  * written instead of where it is read).  Needs 16-byte aligned bases and K, ldb, row / batch strides % 8 == 0.
  * C.base may be NULL (with C16 given and a non-accumulating epilogue): the result then exists only as the shadow -- the
- * strides of C still describe the layout -- which halves to thirds the bytes an intermediate activation costs. */
+ * strides of C still describe the layout -- which halves to thirds the bytes an intermediate activation costs.
+ * Extents (lidbox_gemm_bf16s_nt and _tn alike): any extent is legal.  The LDS-DMA, ping-pong and K-resident kernels address an
+ * operand with 32-bit byte offsets and are chosen while its extent in bytes, (batch - 1) batch_stride + rows_per_batch row_stride
+ * + width (B16: N ldb + K) times 2, stays below 4.0e9 (the K-resident forward kernel also needs one utterance below 2.0e9);
+ * beyond, the register-staged / four-wave kernels run. */
 int lidbox_gemm_bf16s_nt(lidbox_rows_t A16, const void* B16, long ldb, lidbox_rows_out_t C, void* C16,
                          int K, int N, int epilogue, const float* aux,
                          void* workspace, size_t workspace_bytes, lidbox_stream_t stream);
@@ -424,8 +433,9 @@ int lidbox_gemm_bf16s_last_pair(void);
 int lidbox_gemm_bf16s_tn_last_pp(void);
 /* ... and the number of utterance slices of the K1-resident kernel (gemm16_tn_kres.h, round 6) if that ran, else 0: a contraction
  * of <= 224 (whole output rows of one workgroup), N a multiple of 128, overlapping or adjacent windows of a batched input whose batch
- * stride is a whole number of row strides -- frame1's wgrad (k = 5, 40 channels: K1 = 200).  LIDBOX_GEMM16_TN_KRES=0 / 1: never /
- * whenever the operands allow. */
+ * stride is a whole number of row strides and reaches less than one row stride beyond the utterance's last window (the kernel
+ * reads every element in between against zero rows of dY: elements no window covers must not reach it) -- frame1's wgrad (k = 5,
+ * 40 channels: K1 = 200).  LIDBOX_GEMM16_TN_KRES=0 / 1: never / whenever the operands allow. */
 int lidbox_gemm_bf16s_tn_last_kres(void);
 /* The bf16 families' planner as a query (tests, profiling tools): launches nothing and needs no device.  It runs the functions the
  * launches run and reports what a call with these arguments would do; pointers are only tested for alignment and NULL.

@@ -1526,13 +1526,18 @@ Tn16sPlan plan_tn16s(const lidbox_rows_t& A16, const lidbox_rows_t& B16, long M,
         pp.use = false;
     // the K1-resident kernel (gemm16_tn_kres.h): short contraction over overlapping windows, the whole K1 extent in one workgroup's
     // accumulators.  It walks the input as one flattened sequence of rows: utterances a whole number of row strides apart, at least as
-    // many of those as output rows, one stage's frames inside its LDS image; same utterance structure on both operands.
+    // many of those as output rows, one stage's frames inside its LDS image; same utterance structure on both operands.  It reads
+    // EVERY element between an utterance's first window and the next utterance's (the rows in between meet zero rows of dY, and
+    // 0 x NaN is NaN): the windows of an utterance must reach the next utterance to within one row stride, as a causal Conv1D's
+    // do (a strided one leaves less than a stride of its input behind its last window) -- a batch stride stretched further leaves
+    // whole rows no window covers (undefined for the caller) and takes the four-wave kernel.
     const TnKresPlan kp = plan_tn16_kres(M, K1, N);
     // (slices are ranges of utterances: with fewer utterances than half the slices the chip would be mostly idle)
     const bool desc_ok = kp.shape_ok && (kp.forced || 2 * A16.batch >= kp.max_slices) && A16.batch == B16.batch &&
                          A16.rows_per_batch == B16.rows_per_batch &&
                          A16.row_stride > 0 && (A16.batch == 1 || A16.batch_stride % A16.row_stride == 0) &&
                          (A16.batch == 1 || A16.batch_stride / A16.row_stride >= A16.rows_per_batch) &&
+                         (A16.batch == 1 || A16.batch_stride < (long)A16.rows_per_batch * A16.row_stride + K1) &&
                          63 * A16.row_stride + K1 <= TKR_IMG_ELEMS &&
                          (63 + lbx_cdiv(K1, A16.row_stride)) * tkr_img_stride((int)A16.row_stride) <= TKR_IMG_BYTES && span_ok(A16, K1) &&
                          span_ok(B16, N);

@@ -40,7 +40,10 @@ helpers are imported, not copied.
 Largest err / bound seen on the device (one run on one MI355X; per kernel in the docstring of tests/test_gemm16_paths_gpu.py): 0.087
 (gemm16s_rows_dma_kernel<128,64,2>); every `exact` case bit-equal, fp32 and shadow.  The CPU emulation's largest figure is 0.087 too.
 
-Out of scope: the 32-bit-extent refusals (a_ext, b_ext, span_ok beyond 4e9 need allocations above 4 GB).
+The 32-bit-extent terms (a_ext, b_ext, a_span with its per-utterance limit, span_ok, pp2_problem's a_ext / b_ext) are restated
+with their limits READ from gemm_bf16.hip (limits16); PATHS["FAR16"] holds rows on both sides of each, found by stretching one
+stride of a descriptor.  The planner only looks at the descriptors, so tests/test_oracle_gemm16_paths.py pins both sides of
+every limit on the CPU through lidbox_gemm_bf16_plan_query.
 """
 import os
 import re
@@ -193,6 +196,42 @@ def dma_branch(M, N, K, writes_fp32):
     return "default_64x128"
 
 
+_LIM16 = None
+
+
+def limits16():
+    """the byte limits of the 32-bit-extent terms, read from gemm_bf16.hip"""
+    global _LIM16
+    if _LIM16 is None:
+        with open(os.path.join(_CSRC, "gemm_bf16.hip")) as fh:
+            src = fh.read()
+        span = re.search(r"a_span < ([0-9.e]+) && tiles_n <= NUM_CU &&\s*\(\(double\)\(A\.rows_per_batch - 1\) \* \(double\)A\.row_stride \+ K\) \* 2\.0 < ([0-9.e]+);", src)
+        ext = re.findall(r"a_ext < ([0-9.e]+) && b_ext < ([0-9.e]+)", src)
+        sp = re.search(r"return r\.batch_stride >= 0 && r\.row_stride >= 0 && span < ([0-9.e]+);", src)
+        assert span and len(ext) == 2 and sp, "an extent term of gemm_bf16.hip no longer reads as restated here"
+        _LIM16 = dict(a_span=float(span.group(1)), a_utt=float(span.group(2)), a_ext=float(ext[0][0]), b_ext=float(ext[0][1]),
+                      pair_a_ext=float(ext[1][0]), pair_b_ext=float(ext[1][1]), span=float(sp.group(1)))
+    return _LIM16
+
+
+def a_ext16(a, K):
+    """a_ext (and a_span: the same expression) of plan_rows16s / pp2_problem, bytes"""
+    return (float(a["batch"] - 1) * float(a["bs"]) + float(a["rpb"]) * float(a["rs"]) + K) * 2.0
+
+
+def a_utt16(a, K):
+    """the per-utterance term of the K-resident `can`"""
+    return (float(a["rpb"] - 1) * float(a["rs"]) + K) * 2.0
+
+
+def b_ext16(N, ldb, K):
+    return (float(N) * float(ldb) + K) * 2.0
+
+
+def span16(d, w):
+    return (float(d["batch"] - 1) * float(d["bs"]) + float(d["rpb"] - 1) * float(d["rs"]) + w) * 2.0
+
+
 def kres_applies(a, K, N):
     if not (K % 8 == 0 and 16 <= K <= _c("KRES_KMAX") and a["batch"] >= 1 and a["rpb"] >= 1):
         return False
@@ -226,7 +265,9 @@ def kres_conditions(a, c, K, N, epi, has_mask16, carries, c_res=0, c16_res=0):
         no_mask16=not has_mask16,
         applies=kres_applies(a, K, N),
         bs_nonneg=a["bs"] >= 0,
-        tiles_n=tiles_n <= NUM_CU)
+        a_span=a_ext16(a, K) < limits16()["a_span"],
+        tiles_n=tiles_n <= NUM_CU,
+        a_utt=a_utt16(a, K) < limits16()["a_utt"])
 
 
 def plan_rows16s(a, ldb, c, K, N, epi, has_mask16, carries, wsb, env, c_null=False, c_res=0, c16_res=0):
@@ -238,7 +279,7 @@ def plan_rows16s(a, ldb, c, K, N, epi, has_mask16, carries, wsb, env, c_null=Fal
     if can and (mode == 1 or (a["rs"] * 2 <= K and a["batch"] * tiles_n >= 2 * NUM_CU)):
         return dict(kernel=KS_KRES13 if (K + 15) // 16 == 13 else KS_KRES0)
     dc = choose_dma16(M, N, K, wsb, not c_null, env)
-    if dc["bm"] != 0:
+    if dc["bm"] != 0 and a_ext16(a, K) < limits16()["a_ext"] and b_ext16(N, ldb, K) < limits16()["b_ext"]:
         return dict(kernel=KS_PP if dc["bm"] == 256 else KS_DMA, dc=dc)
     pl = plan_rows16(M, N, K, wsb, _c("BKS"))
     return dict(kernel=KS_ROWS, pl=pl, tail=plan_tail16(pl, M, N, K, wsb, _c("BKS"), _c("WAVES_S") * NUM_CU))
@@ -286,8 +327,7 @@ def tkr_img_stride(rs):
 
 
 def span_ok(d, w):
-    span = ((d["batch"] - 1) * d["bs"] + (d["rpb"] - 1) * d["rs"] + w) * 2.0
-    return d["bs"] >= 0 and d["rs"] >= 0 and span < 4.0e9
+    return d["bs"] >= 0 and d["rs"] >= 0 and span16(d, w) < limits16()["span"]
 
 
 def tn_pp_conditions(a, b, K1, N):
@@ -301,7 +341,8 @@ def tn_kres_conditions(a, b, K1, N, kp):
     rs = a["rs"]
     return dict(shape_ok=kp["shape_ok"], enough_utts=kp["forced"] or 2 * a["batch"] >= kp["max_slices"], same_batch=a["batch"] == b["batch"],
                 same_rpb=a["rpb"] == b["rpb"], rs_pos=rs > 0, bs_whole=rs > 0 and (a["batch"] == 1 or a["bs"] % rs == 0),
-                bs_covers=rs > 0 and (a["batch"] == 1 or a["bs"] // rs >= a["rpb"]), img_elems=63 * rs + K1 <= _c("TKR_IMG_ELEMS"),
+                bs_covers=rs > 0 and (a["batch"] == 1 or a["bs"] // rs >= a["rpb"]),
+                gap_covered=a["batch"] == 1 or a["bs"] < a["rpb"] * rs + K1, img_elems=63 * rs + K1 <= _c("TKR_IMG_ELEMS"),
                 img_bytes=rs > 0 and (63 + cdiv(K1, rs)) * tkr_img_stride(rs) <= _c("TKR_IMG_BYTES"), span_a=span_ok(a, K1), span_b=span_ok(b, N))
 
 
@@ -390,14 +431,15 @@ def pp2_conditions(call, wsb, env):
     M = a["batch"] * a["rpb"]
     dc = choose_dma16(M, N, K, wsb, not call.get("c_null", False), env) if M > 0 and N > 0 and K > 0 else dict(bm=0, bn=0, stages=0, splits=1)
     if not (M > 0 and N > 0 and K > 0):                            # the first test of pp2_problem: nothing behind it is evaluated
-        return dict(nonempty=False, shadow_only_ok=True, mask16_epi=True, aligned=True, not_kres=True, pp256_unsplit=True)
+        return dict(nonempty=False, shadow_only_ok=True, mask16_epi=True, aligned=True, not_kres=True, pp256_unsplit=True, ext=True)
     return dict(nonempty=True,
                 shadow_only_ok=not call.get("c_null", False) or (call.get("shadow", True) and epi not in EPI_ACCUMS),
                 mask16_epi=not call.get("mask16", False) or epi in EPI_HAS_MASK,
                 aligned=rows16s_operands_ok(a, call.get("a_res", 0), call.get("b_res", 0), call.get("ldb", K), c, call.get("c_res", 0),
                                             0 if call.get("shadow", True) else None, K, 0),
                 not_kres=call.get("mask16", False) or not kres_applies(a, K, N),
-                pp256_unsplit=(dc["bm"], dc["bn"], dc["stages"], dc["splits"]) == (256, 256, 2, 1))
+                pp256_unsplit=(dc["bm"], dc["bn"], dc["stages"], dc["splits"]) == (256, 256, 2, 1),
+                ext=a_ext16(a, K) < limits16()["pair_a_ext"] and b_ext16(N, call.get("ldb", K), K) < limits16()["pair_b_ext"])
 
 
 def plan_query(kind, a, b, c, K, N, epi, env, wsb, has_ws=True, res=None, c_null=False, shadow=True, mask16=False, njobs=0, bias_grad=True,
@@ -1131,9 +1173,9 @@ def _tn16s_table():
                      _conv(19, 9, 8, 2, 1), b=_batched(19, 9, 4096, 0, 0), env=KR1, expect=dict(kernel=KS_TN_KRES, splits=7, ups=3)))
     for name, why, a, b in (
             ("rpb", "rows_per_batch differ", _conv(4, 70, 40, 5, 1), _batched(5, 56, 128, 0, 0)),
-            ("bs-whole", "batch_stride no whole number of row strides", dict(batch=4, rpb=70, rs=40, bs=74 * 40 + 8), _batched(4, 70, 128, 0, 0)),
+            ("bs-whole", "batch_stride no whole number of row strides", dict(batch=4, rpb=70, rs=40, bs=74 * 40 - 8), _batched(4, 70, 128, 0, 0)),
             ("bs-covers", "batch_stride / row_stride < rows_per_batch", dict(batch=4, rpb=70, rs=40, bs=40 * 40), _batched(4, 70, 128, 0, 0)),
-            ("img", "63 row strides + K1 beyond the stage image", dict(batch=4, rpb=70, rs=64, bs=74 * 64), _batched(4, 70, 128, 0, 0))):
+            ("img", "63 row strides + K1 beyond the stage image", dict(batch=4, rpb=70, rs=64, bs=72 * 64), _batched(4, 70, 128, 0, 0))):
         T.append(_tn_row("TN16S", "s-tn-kres-refuse-" + name, "plan_tn16s: desc_ok false by %s -> the four-wave kernel" % why, "s", 200, 128, a, b=b, env=KR1,
                          expect=dict(kernel=KS_TN)))
     T.append(_tn_row("TN16S", "s-tn-kres-ws", "plan_tn16s: a workspace too small for 5 utterance slices but enough for plan_tn16's 2 -> the four-wave kernel", "s", 200, 128,
@@ -1299,6 +1341,90 @@ def _bigtn16s_table():
 PATHS = dict(ROWS16=_rows16_table(), TN16=_tn16_table(), ROWS16S=_rows16s_table(), TN16S=_tn16s_table(), PAIR16S=_pair16s_table(),
              CARRY16S=_carry16s_table(), CONVERT=_convert_table(), BIG16S=_big16s_table(), BIGTN16S=_bigtn16s_table())
 
+def _far16_table():
+    """rows on both sides of every 32-bit-extent term of the storage planners, found by stretching one stride ('bs', 'rs' or 'ldb') of
+    a small problem into a zone (gp.ZONES) of the term's own expression.  far: operand -> stride; term: the limit of limits16();
+    expect: the kernel the restated planner and the export must name."""
+    T = []
+    L = limits16()
+    # two utterances one after the other: the second starts behind the last window of the first
+    pair = lambda rpb, w, rs=None: dict(batch=2, rpb=rpb, rs=w if rs is None else rs, bs=cdiv((rpb - 1) * (w if rs is None else rs) + w, 8) * 8)
+
+    def solve(mk, g, term, zone, step=8, lo=8):
+        return mk(gp._solve(lambda s: g(mk(s)), L[term], zone, step=step, lo=lo))
+
+    # rows: the LDS-DMA tile (the policy's own 64 x 64 x 2), the ping-pong tile (forced 256 x 128 x 2), the K-resident kernel
+    # (LIDBOX_GEMM16S_KRES=1)
+    for kname, kern, env, a0, N, K in (("dma", KS_DMA, {}, pair(65, 64), 64, 64),
+                                       ("pp", KS_PP, {"LIDBOX_GEMM16S_DMA": "256,128,2"}, pair(129, 64), 64, 64),
+                                       ("kres0", KS_KRES0, {"LIDBOX_GEMM16S_KRES": "1"}, pair(65, 40, 8), 64, 40)):
+        term = "a_span" if kern == KS_KRES0 else "a_ext"
+        for zone in ("over", "edge-out", "edge-in", "high"):
+            a = solve(lambda s: dict(a0, bs=s), lambda d: a_ext16(d, K), term, zone, lo=a0["bs"])
+            fast = zone in ("high", "edge-in")
+            T.append(_row("FAR16", "far16-%s-A-bs-%s" % (kname, zone), "plan_rows16s: %s %s %.1e by batch_stride (%s)" % (term, "<" if fast else ">=", L[term], zone),
+                          "s", "nt", N, K, a, c=_batched(2, a0["rpb"], N), env=env, ws="plan", zone=zone, far={"A": "bs"}, term=term,
+                          expect=dict(kernel=kern if fast else None, not_kernel=None if fast else kern)))
+    # the K-resident kernel's per-utterance limit: one utterance of 1.25e8 windows 8 elements apart (planner only: no device could
+    # hold its C); the total a_span stays below its own limit
+    for zone in ("over", "edge-out", "edge-in", "high"):
+        mk = lambda s: dict(batch=1, rpb=s, rs=8, bs=0)
+        a = solve(mk, lambda d: a_utt16(d, 40), "a_utt", zone, step=1, lo=1)
+        fast = zone in ("high", "edge-in")
+        T.append(_row("FAR16", "far16-kres0-A-utt-%s" % zone, "plan_rows16s: the per-utterance term of `can` %s %.1e (%s)" % ("<" if fast else ">=", L["a_utt"], zone),
+                      "s", "nt", 64, 40, a, env={"LIDBOX_GEMM16S_KRES": "1"}, ws="none", zone=zone, far={"A": "rpb"}, term="a_utt", planner_only=True,
+                      expect=dict(kernel=KS_KRES0 if fast else None, not_kernel=None if fast else KS_KRES0)))
+    # b_ext by ldb on the LDS-DMA tile
+    for zone in ("over", "edge-out", "edge-in", "high"):
+        ldb = gp._solve(lambda s: b_ext16(64, s, 64), L["b_ext"], zone, step=8, lo=64)
+        fast = zone in ("high", "edge-in")
+        T.append(_row("FAR16", "far16-dma-B-ldb-%s" % zone, "plan_rows16s: b_ext %s %.1e by ldb (%s)" % ("<" if fast else ">=", L["b_ext"], zone), "s", "nt", 64, 64,
+                      _dense(130, 64), env={}, ws="plan", ldb_pad=ldb - 64, zone=zone, far={"B": "ldb"}, term="b_ext",
+                      expect=dict(kernel=KS_DMA if fast else KS_ROWS, not_kernel=None if fast else KS_DMA)))
+    # wgrads: the ping-pong tile (LIDBOX_GEMM16_TN_PP=1) and the K1-resident kernel (LIDBOX_GEMM16_TN_KRES=1), span_ok on either operand
+    for kname, kern, env, rpb, K1, N, rs in (("tn_pp", KS_TN_PP, {"LIDBOX_GEMM16_TN_PP": "1", "LIDBOX_GEMM16_TN_KRES": "0"}, 512, 64, 64, 64),
+                                             ("tn_kres", KS_TN_KRES, {"LIDBOX_GEMM16_TN_KRES": "1", "LIDBOX_GEMM16_TN_PP": "0"}, 64, 40, 128, 8)):
+        for op in ("A", "B"):
+            for zone in ("over", "edge-out", "edge-in", "high"):
+                a0, b0 = pair(rpb, K1, rs), pair(rpb, N)
+                w = K1 if op == "A" else N
+                step = rs if (kern == KS_TN_KRES and op == "A") else 8          # the K1-resident kernel: utterances whole row strides apart
+                far = solve(lambda s: dict(a0 if op == "A" else b0, bs=s), lambda d: span16(d, w), "span", zone, step=step, lo=(a0 if op == "A" else b0)["bs"])
+                a, b = (far, b0) if op == "A" else (a0, far)
+                fast = zone in ("high", "edge-in")
+                why = "plan_tn16s: span_ok(%s) %s by batch_stride (%s)" % (op, "true" if fast else "false", zone)
+                if kern == KS_TN_KRES and op == "A":
+                    # the K1-resident kernel reads every element between two utterances' first windows: a stretched batch stride of
+                    # its A leaves elements no window covers and is refused (gap_covered) on both sides of span_ok's limit
+                    fast, why = False, why + "; gap_covered false first -> the four-wave kernel"
+                T.append(_tn_row("FAR16", "far16-%s-%s-bs-%s" % (kname, op, zone), why, "s", K1, N, a, b=b, env=env, zone=zone, far={op: "bs"}, term="span",
+                                 twin_same=fast, expect=dict(kernel=kern if fast else KS_TN, not_kernel=None if fast else kern)))
+    # the K1-resident kernel's own gap term at its edge: the next utterance begins where the windows of this one end / one row stride on
+    for name, extra, fast in (("in", 0, True), ("out", 8, False)):
+        a = dict(batch=2, rpb=64, rs=8, bs=63 * 8 + 40 + extra)
+        T.append(_tn_row("FAR16", "far16-tn_kres-gap-" + name, "plan_tn16s: batch_stride %s rpb rs + K1 -> %s" % ("<" if fast else "==", "K1-resident" if fast else "four-wave"),
+                         "s", 40, 128, a, b=pair(64, 128), env={"LIDBOX_GEMM16_TN_KRES": "1", "LIDBOX_GEMM16_TN_PP": "0"}, zone="edge-in" if fast else "edge-out",
+                         far={}, term="gap", twin_same=fast, expect=dict(kernel=KS_TN_KRES if fast else KS_TN, not_kernel=None if fast else KS_TN_KRES)))
+    return T
+
+
+PATHS["FAR16"] = _far16_table()
+
+
+def far16_pair_calls():
+    """pp2_problem's a_ext / b_ext (the second site): a call that joins a two-problem grid, then stretched over either limit alone"""
+    M, N, K = 256 * 192, 256, 512
+    base = dict(a=_dense(M, K), c=_dense(M, N), K=K, N=N, epi=EPI_NONE, ldb=K)
+    L = limits16()
+    out = [("far16-pair-in", base, True)]
+    for zone in ("edge-in", "edge-out", "over"):
+        rs = gp._solve(lambda s: a_ext16(dict(batch=1, rpb=M, rs=s, bs=0), K), L["pair_a_ext"], zone, step=8, lo=K)
+        out.append(("far16-pair-A-rs-%s" % zone, dict(base, a=dict(batch=1, rpb=M, rs=rs, bs=0)), zone == "edge-in"))
+        ldb = gp._solve(lambda s: b_ext16(N, s, K), L["pair_b_ext"], zone, step=8, lo=K)
+        out.append(("far16-pair-B-ldb-%s" % zone, dict(base, ldb=ldb), zone == "edge-in"))
+    return out
+
+
 # policy branches no row selects, with the reason
 UNREACHED = [
     dict(what="choose_dma16: `t128 >= 3 * NUM_CU` in the K >= 1536 branch",
@@ -1309,7 +1435,8 @@ UNREACHED = [
          why="each of them is a test lidbox_gemm_bf16s_nt_carry makes too (C.base == NULL needs the shadow and a non-accumulating epilogue; "
              "LIDBOX_EPI_MASK_BF16 goes with a ReLU-mask epilogue; validate_rows_call; rows16s_operands_ok), so the two-call path the pair "
              "entry falls back to refuses the same call: there are no two results to compare.  The terms that can fail alone and still run "
-             "have rows: M == 0 (pair-empty), kres_applies (pair-kres), the tile / split (pair-small, pair-split); a_ext / b_ext need 4 GB."),
+             "have rows: M == 0 (pair-empty), kres_applies (pair-kres), the tile / split (pair-small, pair-split); a_ext / b_ext: FAR16 "
+             "(far16-pair-*, pinned on the CPU through pp2_conditions)."),
     dict(what="plan_rows16s: a bf16 mask as the ONLY failing condition of the K-resident `can`",
          why="LIDBOX_EPI_MASK_BF16 is accepted with a ReLU-mask epilogue only, and epi_ok refuses those epilogues: the two fail together "
              "(row kres-refuse-mask)"),

@@ -35,10 +35,17 @@ numpy only; tests/test_oracle_gemm_paths.py checks every restated function again
    (lidbox_gemm_tn_partial -> lidbox_gemm_nt_carry, lidbox_zero_job).  Each row names the source condition it is there for in
    `why`.  Shapes were found by searching the restated planner: the smallest that still select their path.
 
+7. The 32-bit extent guards: limits() reads the limits of sk_extent_ok, sk_b_extent_ok, reduce_job_vec_ok and the inner test of
+   store_rows_tile from the source; the guards restated and threaded through rows_dispatch / tn_dispatch / pair_plan; PATHS["FAR"]
+   (rows in the zones high / edge-in / edge-out / over of a guard's own expression, C-far rows, the pair and reduce-job rows);
+   far_layout, the sparse judge judge_far_rows, and the planted ADDRESSING_MISTAKES on an emulated far gather / scatter.
+
 Largest err / bound seen on the device (one run on one MI355X; the figures per kernel stand in the docstring of
 tests/test_gemm_paths_gpu.py): 0.21 (gemm_rows_kernel, K = 36 .. 52); every `exact` case bit-equal.
 
-Out of scope here: the 32-bit-extent refusals (sk_extent_ok, sk_b_extent_ok need allocations above 4 GB).  The bf16 families
+The 32-bit-extent guards (sk_extent_ok, sk_b_extent_ok, reduce_job_vec_ok's byte limit, the inner test of store_rows_tile) are
+restated in section 7 with their limits READ from the source; PATHS["FAR"] holds the rows on both sides of each, which
+tests/test_gemm_far_gpu.py runs in sparse allocations (tests/far_buffers.py).  The bf16 families
 (gemm_bf16.hip, gemm16_*.h) have their own module, oracle/gemm16_paths_np.py, which imports this one's helpers.
 lidbox_gemm_nt_tn_carry with pending jobs stays with tests/test_gemm_sk_gpu.py (bit identity).
 """
@@ -345,8 +352,9 @@ def _range_launch(out, ch, kind, al, dma_ok, env, stream_g=0):
 
 
 def rows_dispatch(kind, M, N, K, al, ws_bytes, env, epi=EPI_NONE, ws_al=True, c_batch=1, c_rpb=0, c_rs=None, c_bs=0, c_res=0,
-                  aux_res=0):
-    """what launch_rows does: dict(family, kernels, launches, g, p, sk, tail_split, ch)"""
+                  aux_res=0, a_ext=True, b_ext=True):
+    """what launch_rows does: dict(family, kernels, launches, g, p, sk, tail_split, ch).  a_ext / b_ext: sk_extent_ok(A, K) and
+    sk_b_extent_ok(B_KINNER, K, N, ldb) of the call (section 7; True for every operand far below the limits)"""
     out = dict(family=0, kernels=[], launches=[0, 0, 0], g=0, p=1, sk=None, tail_split=False, ch=None, first_tile=None)
     if M == 0 or N == 0:
         return out
@@ -354,13 +362,13 @@ def rows_dispatch(kind, M, N, K, al, ws_bytes, env, epi=EPI_NONE, ws_al=True, c_
     ch = choose_rows_env(kind, M, N, K, wsb, env)
     out["ch"] = ch
     c_rs = N if c_rs is None else c_rs
-    if al and "LIDBOX_GEMM_PLAN" not in env and ws_al and not sk_tuned_out(kind, M, N, K, env):
+    if al and "LIDBOX_GEMM_PLAN" not in env and ws_al and not sk_tuned_out(kind, M, N, K, env) and b_ext:
         has_mask = epi in EPI_HAS_MASK
         skp_ok = (skp_mode(env) != 0 and (c_batch == 1 or c_rpb >= 32) and N % 4 == 0 and c_res == 0 and c_rs % 4 == 0
                   and (c_batch == 1 or c_bs % 4 == 0) and (not has_mask or aux_res == 0) and skp_mode(env) == 2)
         for pipelined in ((True, False) if skp_ok else (False,)):
             sk = sk_rows_plan(kind, M, N, K, env, pipelined)
-            if sk is not None and wsb >= sk["ws_need"]:
+            if sk is not None and wsb >= sk["ws_need"] and a_ext:
                 out.update(family=2, launches=[1, 0, 0], sk=sk, p=sk["p"], first_tile=(SK_BM, SK_BN))
                 if pipelined:
                     out["kernels"] = ["gemm_skp_rows_kernel<%s,%s,%s>" % (_kin(kind), "mask" if has_mask else "nomask",
@@ -368,7 +376,7 @@ def rows_dispatch(kind, M, N, K, al, ws_bytes, env, epi=EPI_NONE, ws_al=True, c_
                 else:
                     out["kernels"] = ["gemm_sk_rows_kernel<%s>" % _kin(kind)]
                 return out
-    dma_ok = al
+    dma_ok = al and a_ext and b_ext
     if dma_ok and dma_mode(env) != 0 and ch["splits"] == 1 and ws_al:
         spl = dma_stream_plan(ch["bm"], ch["bn"], M, N, K, env)
         if spl["g"] > 1 and wsb >= spl["ws_need"]:
@@ -490,21 +498,22 @@ def reduce_job_vec_ok(p_res, splits, K1, N, c_res, ldc, bias_grad, bg_res=0):
     n = K1 * N
     pc_res = (p_res + 4 * splits * n) % 16
     return (N % 4 == 0 and ldc % 4 == 0 and n % 4 == 0 and p_res == 0 and c_res == 0 and
-            (not bias_grad or (pc_res == 0 and bg_res == 0)) and splits * n * 4.0 < 4.0e9)
+            (not bias_grad or (pc_res == 0 and bg_res == 0)) and job_guard(splits, n) < limits()["job_bytes"])
 
 
-def tn_dispatch(M, K1, N, a_al, b_al, ws_bytes, env, ws_res=0, c_res=0, ldc=None, bias_grad=True, bg_res=0):
-    """what tn_partial_launch + run_reduce_jobs do: dict(family, kernels, launches, splits, rps)"""
+def tn_dispatch(M, K1, N, a_al, b_al, ws_bytes, env, ws_res=0, c_res=0, ldc=None, bias_grad=True, bg_res=0, a_ext=True, b_ext=True):
+    """what tn_partial_launch + run_reduce_jobs do: dict(family, kernels, launches, splits, rps).  a_ext / b_ext:
+    sk_extent_ok(A, K1) and sk_extent_ok(Bd, N), tested at the stream-K gate and again at the LDS-DMA gate"""
     ldc = N if ldc is None else ldc
     sk = sk_tn_plan(M, K1, N, env)
     if (sk is not None and "LIDBOX_GEMM_TN_PLAN" not in env and not sk_tuned_out(2, M, N, K1, env) and ws_res == 0 and
-            ws_bytes >= sk["ws_need"] and a_al and b_al):
+            ws_bytes >= sk["ws_need"] and a_al and b_al and a_ext and b_ext):
         fam, kern, splits, rps = 2, "gemm_sk_tn_kernel", sk["splits"], sk["rps"]
     else:
         pl = tn_plan(M, K1, N, env)
         splits, rps = pl["splits"], pl["rps"]
         al = a_al and b_al and K1 % 4 == 0 and N % 4 == 0
-        if al and dma_mode(env) != 0 and rps % SK_BK == 0:
+        if al and dma_mode(env) != 0 and a_ext and b_ext and rps % SK_BK == 0:
             fam, kern = 1, "gemm_tn_dma_kernel<%d,%d>" % (pl["bm"], pl["bn"])
         else:
             fam, kern = 0, "gemm_tn_kernel<%d,%d,%s>" % (pl["bm"], pl["bn"], "al" if al else "un")
@@ -513,8 +522,11 @@ def tn_dispatch(M, K1, N, a_al, b_al, ws_bytes, env, ws_res=0, c_res=0, ldc=None
                 splits=splits, rps=rps, p=splits)
 
 
-def pair_plan(M, Co, N, K1, ws_nt_bytes, ws_tn_bytes, env):
-    """pair_plan / lidbox_gemm_plan_is_pair: (ch, pl) or None"""
+def pair_plan(M, Co, N, K1, ws_nt_bytes, ws_tn_bytes, env, al_rows=True, al_tn=True):
+    """pair_plan / lidbox_gemm_plan_is_pair: (ch, pl) or None.  al_rows / al_tn: the two operand predicates of lidbox_gemm_nt_tn in
+    front of pair_plan (pair_al_rows, pair_al_tn), each refusing the pair on its own"""
+    if not (al_rows and al_tn):
+        return None
     if dma_mode(env) == 0 or "LIDBOX_GEMM_NO_PAIR" in env or min(M, N, K1, Co) < 1 or Co % 4 != 0 or K1 % 4 != 0:
         return None
     ch = choose_rows_env(1, M, N, Co, ws_nt_bytes, env)
@@ -1398,3 +1410,383 @@ def instantiations_from_source():
         assert not a, (kernel, a)
         return kernel
     return sorted(spell(k, a) for k, a in found)
+
+
+# ------------------------------------------------------------------------------------------------ 7. the 32-bit extent guards
+# The LDS-DMA kernels address an operand with one 64-bit base and a 32-bit byte offset per lane; the host lets them run while
+# the guard's expression g stays below its limit L (bytes, 4.0e9: above 2^31, so offsets with bit 31 set are legal).  The limits
+# are READ from the source text, like the tuned table.  FAR rows put an operand across a limit by stretching one stride, so a
+# case stays at a few MFLOP while its last row lies 4 GB behind the base.
+_LIMITS = None
+ZONES = ("high", "edge-in", "edge-out", "over")
+HIGH_BYTES = 3.9e9                                                  # `high`: the largest byte offset dereferenced is at least this
+OVER = 1.05
+
+
+def limits():
+    """the numeric limits of the guards, from csrc/gemm.hip and csrc/gemm_shared.h"""
+    global _LIMITS
+    if _LIMITS is None:
+        here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "lidbox_amd", "csrc")
+        with open(os.path.join(here, "gemm.hip")) as f:
+            src = f.read()
+        with open(os.path.join(here, "gemm_shared.h")) as f:
+            sh = f.read()
+        a = re.search(r"inline bool sk_extent_ok\(.*?\+ cols \+ (\d+);\s*return last \* 4\.0 < ([0-9.e]+);", src, re.S)
+        b = re.search(r"inline bool sk_b_extent_ok\(.*?\+ ([0-9.]+)\) \* \(double\)ldb \* 4\.0 < ([0-9.e]+);", src, re.S)
+        j = re.search(r"inline bool reduce_job_vec_ok\(.*?\(double\)splits \* \(double\)n \* 4\.0 < ([0-9.e]+);", sh, re.S)
+        inner = re.findall(r"const bool inner = .*?\(unsigned\)Cd\.rpb >= (\d+)\) &&\s*out_rs > 0 && out_rs < \(1L << (\d+)\) && wrap_u >= 0 && "
+                           r"wrap_u < \(1L << (\d+)\);", sh, re.S)
+        assert a and b and j and inner, "a guard of gemm.hip / gemm_shared.h no longer reads as restated here"
+        assert len(set(inner)) == 1, inner
+        _LIMITS = dict(a_pad=int(a.group(1)), a_bytes=float(a.group(2)), b_pad=float(b.group(1)), b_bytes=float(b.group(2)),
+                       job_bytes=float(j.group(1)), inner_rpb=int(inner[0][0]), inner_rs=1 << int(inner[0][1]), inner_wrap=1 << int(inner[0][2]))
+    return _LIMITS
+
+
+def a_guard(d, cols):
+    """g of sk_extent_ok, in bytes"""
+    last = float(max(d["batch"] - 1, 0)) * d["bs"] + float(max(d["rpb"] - 1, 0)) * d["rs"] + cols + limits()["a_pad"]
+    return last * 4.0
+
+
+def sk_extent_ok(d, cols):
+    return a_guard(d, cols) < limits()["a_bytes"]
+
+
+def b_guard(kind, K, N, ldb):
+    """g of sk_b_extent_ok, in bytes; kind 1 (nt): B[N][ldb], kind 0 (nn): B[K][ldb]"""
+    return (float(N if kind == 1 else K) + limits()["b_pad"]) * float(ldb) * 4.0
+
+
+def sk_b_extent_ok(kind, K, N, ldb):
+    return b_guard(kind, K, N, ldb) < limits()["b_bytes"]
+
+
+def job_guard(splits, n):
+    return float(splits) * float(n) * 4.0
+
+
+def store_inner_ok(c, partial=False):
+    """the descriptor terms of `inner` in store_rows_tile (the per-block terms -- all 32 rows inside M, all columns inside N -- aside)"""
+    L = limits()
+    batched = not partial and c["batch"] != 1
+    wrap = c["bs"] - c["rpb"] * c["rs"] if batched else 0
+    return (not batched or c["rpb"] >= L["inner_rpb"]) and 0 < c["rs"] < L["inner_rs"] and 0 <= wrap < L["inner_wrap"]
+
+
+def pair_al(dy, Co, N, ldb, x, K1, res=None):
+    """(al_rows, al_tn) of lidbox_gemm_nt_tn"""
+    res = res or {}
+    al = lambda d, r: r == 0 and d["rs"] % 4 == 0 and (d["batch"] == 1 or d["bs"] % 4 == 0)
+    al_rows = (al(dy, res.get("dY", 0)) and res.get("W", 0) == 0 and ldb % 4 == 0 and sk_extent_ok(dy, Co) and sk_b_extent_ok(1, Co, N, ldb) and
+               res.get("ws_nt", 0) == 0)
+    return al_rows, al(x, res.get("X", 0)) and sk_extent_ok(x, K1) and res.get("ws_tn", 0) == 0
+
+
+def far_layout(d, cols):
+    """int64 element offsets of the rows of a descriptor whose extent is never materialised (the payload is [M, cols])"""
+    assert cols >= 0
+    return row_offsets(d)
+
+
+def last_byte(d, cols):
+    """the largest byte offset from the base that a row of the descriptor covers"""
+    return (int(far_layout(d, cols).max()) + cols) * 4 - 1
+
+
+def _solve(g, L, zone, step=4, lo=4):
+    """a stride (multiple of `step`) in `zone` of the guard g(stride) < L, g increasing in the stride"""
+    def last_in(lim):
+        a, b = lo // step, 1 << 40
+        assert g(a * step) < lim, "no stride is inside"
+        while b - a > 1:
+            m = (a + b) // 2
+            a, b = (m, b) if g(m * step) < lim else (a, m)
+        return a * step
+    if zone == "edge-in":
+        return last_in(L)
+    if zone == "edge-out":
+        return last_in(L) + step
+    if zone == "over":
+        return last_in(OVER * L) + step
+    return last_in(0.9975 * L)                                      # high: g just below the limit, well inside
+
+
+def stretch(d, cols, which, zone):
+    """the descriptor with stride `which` ('bs' | 'rs') stretched into `zone` of sk_extent_ok"""
+    assert which in ("bs", "rs") and (which == "rs" or d["batch"] > 1)
+    mk = lambda s: dict(d, **({"bs": s} if which == "bs" else {"rs": s, "bs": d["rpb"] * s if d["batch"] > 1 else 0}))
+    return mk(_solve(lambda s: a_guard(mk(s), cols), limits()["a_bytes"], zone, lo=max(4, d[which] if which == "rs" else d["rpb"] * d["rs"])))
+
+
+def stretch_ldb(kind, K, N, zone):
+    return _solve(lambda s: b_guard(KIND[kind], K, N, s), limits()["b_bytes"], zone, lo=(N if kind == "nn" else K))
+
+
+def far_row_predict(r):
+    """rows_dispatch for a FAR row of kind nn / nt: the extent predicates come from the row's own descriptors"""
+    wsb, ws_al = row_ws_bytes(r)
+    c = r["c"]
+    return rows_dispatch(KIND[r["kind"]], r["M"], r["N"], r["K"], row_al(r), wsb, r["env"], r["epi"], ws_al, c["batch"], c["rpb"], c["rs"],
+                         c["bs"], 0, 0, a_ext=sk_extent_ok(r["a"], r["K"]), b_ext=sk_b_extent_ok(KIND[r["kind"]], r["K"], r["N"], ldb_of(r)))
+
+
+def far_tn_predict(r):
+    a, b = r["a"], r["b"]
+    al = lambda d: d["rs"] % 4 == 0 and (d["batch"] == 1 or d["bs"] % 4 == 0)
+    wsb = tn_workspace(r["M"], r["K1"], r["N"], r["env"])
+    return tn_dispatch(r["M"], r["K1"], r["N"], al(a), al(b), wsb, r["env"], 0, 0, r["N"] + r["ldc_pad"], r["bias_grad"], 0,
+                       a_ext=sk_extent_ok(a, r["K1"]), b_ext=sk_extent_ok(b, r["N"]))
+
+
+def compact(d, cols):
+    """the same rows with compact strides"""
+    return dict(batch=d["batch"], rpb=d["rpb"], rs=cols, bs=d["rpb"] * cols if d["batch"] > 1 else 0)
+
+
+def compact_twin(r):
+    """the row with every operand compact: same shape, same environment, same payload"""
+    t = dict(r, name=r["name"] + "@compact", far={}, zone="compact")
+    if r["kind"] == "tn":
+        t.update(a=compact(r["a"], r["K1"]), b=compact(r["b"], r["N"]))
+    else:
+        t.update(a=compact(r["a"], r["K"]), c=compact(r["c"], r["N"]), ldb_pad=0)
+    return t
+
+
+def _far(r, zone, far, expect):
+    r.update(zone=zone, far=far, expect=expect)
+    return r
+
+
+def _far_table():
+    T = []
+    SK16 = dict(SK_ENV, LIDBOX_GEMM_SK_GRID="16")
+    SKP16 = dict(SK16, LIDBOX_GEMM_SKP="2")
+    # kernel -> (env, M as 2 utterances, N, K, ws): the smallest shapes of the ROWS table that select it
+    kernels = [("gemm_sk_rows_kernel", SK16, 250, 200, 520, "lib"), ("gemm_skp_rows_kernel", SKP16, 250, 200, 520, "lib"),
+               ("gemm_rows_dma_kernel", _plan(64, 64), 130, 100, 40, "none"), ("gemm_rows_dma8_kernel", _plan(128, 64, 1, 8), 130, 100, 48, "none"),
+               ("stream", _plan(64, 64), 64 * 33, 512, 256, "stream")]
+
+    def expect(r, fast, kern, fam):
+        """fast side: the named kernel; refused side: the register-staged kernels (family 0)"""
+        if fast:
+            return dict(family=fam, kernel=kern, stream=kern == "stream")
+        return dict(family=0, kernel="gemm_rows")
+
+    fam_of = {"gemm_sk_rows_kernel": 2, "gemm_skp_rows_kernel": 2, "gemm_rows_dma_kernel": 1, "gemm_rows_dma8_kernel": 3, "stream": 1}
+    # 1. nn / nt, A stretched by batch_stride: high and over on every LDS-DMA rows kernel; both edges on one stream-K and one DMA row
+    for kern, env, M, N, K, ws in kernels:
+        for kind in ("nn", "nt"):
+            zones = ["over", "high"]
+            if (kern, kind) in (("gemm_sk_rows_kernel", "nn"), ("gemm_rows_dma_kernel", "nt")):
+                zones = ["over", "edge-out", "edge-in", "high"]
+            for zone in zones:
+                a = stretch(_batched(2, M // 2, K), K, "bs", zone)
+                fast = zone in ("high", "edge-in")
+                T.append(_far(_row("far-A-bs-%s-%s-%s" % (kern.replace("gemm_", "").replace("_kernel", ""), kind, zone),
+                                   "launch_rows: sk_extent_ok(A, K) %s by batch_stride (%s) -> %s" % ("true" if fast else "false", zone, kern if fast else "family 0"),
+                                   kind, N, K, a, epi=EPI_BIAS_RELU if kind == "nn" else EPI_ACCUM, env=env, ws=ws), zone, {"A": "bs"},
+                              expect(None, fast, kern, fam_of[kern])))
+    # 2. the same two kernels, A stretched by row_stride (batch = 1)
+    for kern, env, M, N, K, ws in (kernels[0], kernels[2]):
+        kind = "nn" if kern == "gemm_sk_rows_kernel" else "nt"
+        for zone in ("over", "high"):
+            a = stretch(_dense(M, K), K, "rs", zone)
+            fast = zone == "high"
+            T.append(_far(_row("far-A-rs-%s-%s-%s" % (kern.replace("gemm_", "").replace("_kernel", ""), kind, zone),
+                               "launch_rows: sk_extent_ok(A, K) %s by row_stride, batch = 1 (%s)" % ("true" if fast else "false", zone), kind, N, K, a,
+                               epi=EPI_RELU, env=env, ws=ws), zone, {"A": "rs"}, expect(None, fast, kern, fam_of[kern])))
+    # 3. B stretched by ldb: nt (N rows of ldb floats) and nn (K rows: SkOuter's vo and its 64-bit step); N resp. K = 1024 so that
+    #    the last row of B lies above HIGH_BYTES while (rows + 16) ldb 4 stays below the limit
+    for kern, env, M, _, _, ws in (kernels[0], kernels[2]):
+        for kind in ("nt", "nn"):
+            N, K = (1024, 64 if kern == "gemm_rows_dma_kernel" else 520) if kind == "nt" else (200, 1024)
+            for zone in ("over", "high"):
+                ldb = stretch_ldb(kind, K, N, zone)
+                fast = zone == "high"
+                T.append(_far(_row("far-B-ldb-%s-%s-%s" % (kern.replace("gemm_", "").replace("_kernel", ""), kind, zone),
+                                   "launch_rows: sk_b_extent_ok %s by ldb (%s)" % ("true" if fast else "false", zone), kind, N, K, _dense(M, K),
+                                   epi=EPI_BIAS, env=env, ws=ws, ldb_pad=ldb - (N if kind == "nn" else K)), zone, {"B": "ldb"},
+                              expect(None, fast, kern, fam_of[kern])))
+    # 6. C far, A and B compact: no guard looks at C, the kernels stay on the fast path.  store_rows_tile's inner test at both edges
+    #    of wrap (2^30) and of row_stride (2^25); `off0`: every 32-row block inner and free of a boundary with off0 >= 2^32 bytes.
+    #    rpb = 80 puts a boundary inside the block of rows 64 .. 95 (the wrap32 select); rpb = 96: none.
+    Lm = limits()
+    fams = [("f0", dict(_plan(64, 64), LIDBOX_GEMM_DMA="0"), 0, "gemm_rows_kernel", "none"), ("f1", _plan(64, 64), 1, "gemm_rows_dma_kernel", "none"),
+            ("sk", SK16, 2, "gemm_sk_rows_kernel", "lib"), ("skp", SKP16, 2, "gemm_skp_rows_kernel", "lib")]
+    for fname, env, fam, kern, ws in fams:
+        for sub, c in (("wrap-edge-in", dict(batch=2, rpb=80, rs=1 << 19, bs=80 * (1 << 19) + Lm["inner_wrap"] - 4)),
+                       ("wrap-edge-out", dict(batch=2, rpb=80, rs=1 << 19, bs=80 * (1 << 19) + Lm["inner_wrap"])),
+                       ("off0", dict(batch=2, rpb=96, rs=1 << 19, bs=96 * (1 << 19) + Lm["inner_wrap"] - 4)),
+                       ("rs-edge-in", dict(batch=1, rpb=40, rs=Lm["inner_rs"] - 4, bs=0)), ("rs-edge-out", dict(batch=1, rpb=40, rs=Lm["inner_rs"], bs=0))):
+            if sub.startswith("rs-") and fam == 2:
+                continue                                            # stream-K needs M >= 128: 17 GB of C at this row stride
+            M = c["batch"] * c["rpb"]
+            for epi in (EPI_BIAS_RELU, EPI_RELU_MASK, EPI_ACCUM):
+                kind = "nt" if epi == EPI_ACCUM else "nn"
+                T.append(_far(_row("far-C-%s-%s-e%d" % (sub, fname, epi), "store_rows_tile: C far (%s), no guard on C's extent -> %s stays" % (sub, kern),
+                                   kind, 200, 520 if fam == 2 else 40, _dense(M, 520 if fam == 2 else 40), c=c, epi=epi, env=env, ws=ws), "c-far", {"C": sub},
+                              dict(family=fam, kernel=kern, stream=False)))
+    return T
+
+
+def _far_tn_table():
+    """4. tn: gemm_sk_tn_kernel and gemm_tn_dma_kernel with X far and with dY far, by batch_stride (a_wrap >= 2^29 in SkOuterRows'
+    int arithmetic) and by row_stride (118 rows 2^23 floats apart: a_step = 16 rs >= 2^27)"""
+    T = []
+    for kern, env_bs, env_rs, fam in (("gemm_sk_tn_kernel", dict(SK_ENV, LIDBOX_GEMM_SK_GRID="4"), dict(SK_ENV, LIDBOX_GEMM_SK_GRID="1"), 2),
+                                      ("gemm_tn_dma_kernel", {"LIDBOX_GEMM_TN_PLAN": "64,64,3"}, {"LIDBOX_GEMM_TN_PLAN": "64,64,2"}, 1)):
+        for which in ("bs", "rs"):
+            M, K1, N = (1000, 128, 128) if which == "bs" else (118, 128, 128)
+            for op in ("X", "dY"):
+                for zone in ("over", "high"):
+                    base = _batched(2, M // 2, 128) if which == "bs" else _dense(M, 128)
+                    far = stretch(base, 128, which, zone)
+                    a, b = (far, compact(base, N)) if op == "X" else (compact(base, K1), far)
+                    fast = zone == "high"
+                    r = _tn_row("far-tn-%s-%s-%s-%s" % (kern.replace("gemm_", "").replace("_kernel", ""), op, which, zone),
+                                "tn_partial_launch: sk_extent_ok(%s) %s by %s (%s)" % ("A, K1" if op == "X" else "Bd, N", "true" if fast else "false", which, zone),
+                                K1, N, a, b=b, env=env_bs if which == "bs" else env_rs, accumulate=1 if op == "X" else 0, bias_grad=True)
+                    T.append(_far(r, zone, {op: which}, dict(family=fam if fast else 0, kernel=kern if fast else "gemm_tn_kernel")))
+    return T
+
+
+def _far_pair_table():
+    """5. lidbox_gemm_nt_tn: al_rows refused alone (W's ldb over the limit), al_tn refused alone (X over the limit by batch_stride)"""
+    T = []
+    M, Co, N, K1 = 64, 64, 128, 64
+    T.append(dict(name="far-pair-al_rows", why="lidbox_gemm_nt_tn: only al_rows false (sk_b_extent_ok by ldb) -> the two calls", kind="pair", M=M, Co=Co,
+                  N=N, K1=K1, env={}, ldb=stretch_ldb("nt", Co, N, "over"), x=_dense(M, K1), zone="over", far={"B": "ldb"}, refused="al_rows"))
+    T.append(dict(name="far-pair-al_tn", why="lidbox_gemm_nt_tn: only al_tn false (sk_extent_ok(X, K1) by batch_stride) -> the two calls", kind="pair", M=M,
+                  Co=Co, N=N, K1=K1, env={}, ldb=Co, x=stretch(_batched(2, M // 2, K1), K1, "bs", "over"), zone="over", far={"X": "bs"}, refused="al_tn"))
+    return T
+
+
+def _far_job_table():
+    """7. lidbox_reduce_jobs_run on a hand-made job: N = 1024, n = 2^20; splits = 940: 3.94e9 bytes of slices (high); 960: 4.03e9,
+    over reduce_job_vec_ok's limit yet below 2^32 -- the entry point does not test the limit (only the callers that build a job
+    do), the 16-byte kernel runs and its unsigned scalar offsets k n 4 still fit: the sum must be right"""
+    return [dict(name="far-job-s%d-bp%d-acc%d" % (s, bp, acc), why="reduce_slices: scalar offset k n 4 up to %.3g bytes" % job_guard(s - 1, 1 << 20), kind="job",
+                 N=1024, n=1 << 20, splits=s, bias_partials=bool(bp), accumulate=acc, zone="high" if job_guard(s, 1 << 20) < limits()["job_bytes"] else "over")
+            for s in (960, 940) for bp in (0, 1) for acc in (0, 1)]
+
+
+def far_deref_bytes(r):
+    """operand -> the largest byte offset from its base that the call dereferences"""
+    out = {}
+    if r["kind"] in ("nn", "nt"):
+        out["A"] = last_byte(r["a"], r["K"])
+        brows = r["K"] if r["kind"] == "nn" else r["N"]
+        out["B"] = ((brows - 1) * ldb_of(r) + (r["N"] if r["kind"] == "nn" else r["K"])) * 4 - 1
+        out["C"] = last_byte(r["c"], r["N"])
+    elif r["kind"] == "tn":
+        out["X"], out["dY"] = last_byte(r["a"], r["K1"]), last_byte(r["b"], r["N"])
+    return out
+
+
+def far_guard(r, op):
+    """(g, L) of the guard that looks at operand `op` of the row"""
+    L = limits()
+    if op == "A":
+        return a_guard(r["a"], r["K"]), L["a_bytes"]
+    if op == "B":
+        return b_guard(KIND[r["kind"]], r["K"], r["N"], ldb_of(r)), L["b_bytes"]
+    if op == "X":
+        return a_guard(r["a"], r["K1"]), L["a_bytes"]
+    if op == "dY":
+        return a_guard(r["b"], r["N"]), L["a_bytes"]
+    raise KeyError(op)
+
+
+PATHS["FAR"] = _far_table() + _far_tn_table() + _far_pair_table() + _far_job_table()
+
+
+# -- the sparse judge: the payload [M, N] gathered on the device, and the count of words of C's whole allocation that no longer
+#    hold the fill; never a flat host array
+def judge_far_rows(r, ds, dat, got, changed_words, p):
+    """judge_rows for a far C: `got` the [M, N] payload read through the descriptor, changed_words the number of words of the
+    allocation (margins included) that differ from the NaN fill after the call"""
+    M, N = r["M"], r["N"]
+    got = np.asarray(got, np.float32).reshape(M, N)
+    if changed_words != M * N:
+        return False, np.inf, "words outside the payload were written, or payload words were not (%d changed, %d expected)" % (changed_words, M * N)
+    ref, S = rows_reference(r["kind"], dat["A"], dat["B"], r["epi"], dat["bias"], dat["mask"], dat["old"])
+    if ds == "exact":
+        same = np.array_equal(_bits(got), _bits(ref.astype(np.float32)))
+        return same, 0.0 if same else np.inf, "bits"
+    q = ratio(got, ref, S, chain_n(r["K"], p, r["epi"]))
+    return bool((q <= 1.0).all()), float(q.max()), "bound"
+
+
+# -- planted addressing mistakes on the far layout.  An allocation is [margin][extent][256 bytes] with the base at the start of
+#    the extent and every word NaN but the payload rows; a load is emulated on byte offsets.
+FAR_MARGIN = (1 << 31) + 256
+FAR_TAIL = 256
+ADDRESSING_MISTAKES = ("sign_extended_32", "truncated_mod_2^32", "element_offset_mod_2^31", "limit_in_elements", "wrap32_beyond_2^30")
+
+
+def mistaken_offsets(mut, d, cols):
+    """byte offsets of the rows under the planted mistake (int64), or None where the mistake cannot change any row of d"""
+    off = far_layout(d, cols) * 4
+    last = off + (cols - 1) * 4
+    if mut == "sign_extended_32":                                   # a 32-bit byte offset widened as signed
+        bad = ((off & 0xffffffff) ^ 0x80000000) - 0x80000000
+    elif mut in ("truncated_mod_2^32", "limit_in_elements"):        # 64 -> 32 bits; an element offset that fits, times 4 in 32 bits
+        bad = off & 0xffffffff
+    elif mut == "element_offset_mod_2^31":
+        bad = ((off // 4) & 0x7fffffff) * 4
+    elif mut == "wrap32_beyond_2^30":                               # the select adds (wrap * 4) mod 2^32 behind an utterance boundary
+        if d["batch"] == 1:
+            return None
+        wrap = d["bs"] - d["rpb"] * d["rs"]
+        b = np.arange(d["batch"] * d["rpb"], dtype=np.int64) // d["rpb"]
+        bad = off - b * (wrap * 4) + b * ((wrap * 4) & 0xffffffff)
+    else:
+        raise KeyError(mut)
+    del last
+    return None if np.array_equal(bad, off) else bad
+
+
+def _far_rows_in(d, cols, bad_off):
+    off = far_layout(d, cols) * 4
+    ext = int(off.max()) + cols * 4
+    inside = (bad_off >= -FAR_MARGIN) & (bad_off + cols * 4 <= ext + FAR_TAIL)
+    return off, inside
+
+
+def emulate_far_gather(d, cols, payload, bad_off):
+    """what a kernel reads that forms its row addresses as bad_off: (values [M, cols], left): payload words where a mistaken row
+    lands on payload, NaN (the fill) elsewhere inside the allocation; left = number of rows that left the allocation"""
+    off, inside = _far_rows_in(d, cols, bad_off)
+    order = np.argsort(off)
+    so = off[order]
+    w = bad_off[:, None] + 4 * np.arange(cols, dtype=np.int64)[None, :]          # word by word: a row may straddle a payload row
+    i = np.searchsorted(so, w.ravel(), side="right").reshape(w.shape) - 1
+    rel = w - so[np.maximum(i, 0)]
+    hit = (i >= 0) & (rel < cols * 4) & (rel % 4 == 0) & inside[:, None]
+    out = np.full(w.shape, np.nan, np.float32)
+    out[hit] = np.asarray(payload, np.float32)[order[np.maximum(i, 0)][hit], (rel // 4)[hit]]
+    return out, int((~inside).sum())
+
+
+def emulate_far_scatter(d, cols, result, bad_off, old=None):
+    """what C's true rows hold after a kernel stored `result` through bad_off: (payload read back through the true offsets,
+    changed words in the allocation, left); rows are stored in order, the later row wins"""
+    off, inside = _far_rows_in(d, cols, bad_off)
+    col = 4 * np.arange(cols, dtype=np.int64)[None, :]
+    true_w = (off[:, None] + col).ravel()
+    addr = (bad_off[inside][:, None] + col).ravel()
+    vals = np.asarray(result, np.float32)[inside].ravel()
+    if old is not None:
+        addr, vals = np.concatenate([true_w, addr]), np.concatenate([np.asarray(old, np.float32).ravel(), vals])
+    uniq, first_rev = np.unique(addr[::-1], return_index=True)
+    uv = vals[::-1][first_rev]
+    j = np.searchsorted(uniq, true_w)
+    j = np.minimum(j, max(len(uniq) - 1, 0))
+    got = np.full(true_w.shape, np.nan, np.float32)
+    if len(uniq):
+        hit = uniq[j] == true_w
+        got[hit] = uv[j[hit]]
+    return got.reshape(len(off), cols), int(len(uniq)), int((~inside).sum())

@@ -27,8 +27,8 @@ as a launch of their own (LIDBOX_GEMM_NO_CARRY).  DMA against LIDBOX_GEMM_DMA=0 
 NOT asserted bit-identical (the two operand paths were not read for the same summation order): the al-* and dma-* rows share
 their shapes and are both judged within the bound of the same kind of reference.
 
-Not run here (see the oracle's docstring): the 32-bit-extent refusals, lidbox_gemm_nt_tn_carry with pending jobs, the bf16
-family.
+Not run here: both sides of the 32-bit extent guards (PATHS["FAR"], run by tests/test_gemm_far_gpu.py in sparse allocations),
+lidbox_gemm_nt_tn_carry with pending jobs (tests/test_gemm_sk_gpu.py), the bf16 family (tests/test_gemm16_paths_gpu.py).
 
 Device-side sensitivity, tried once with a scratch build that is not part of the tree: gemm_rows_body made to skip the MFMAs of
 K step 1 when a launch has three or more steps (the planted "dropped interior K step").  Of the 208 ROWS cases exactly the 33

@@ -578,3 +578,105 @@ def test_emulation_inside_and_every_mutation_outside():
     print("emulation worst err / bound %.3f; %d (row, mutation) pairs, uncaught %d; rows per mutation %s" % (worst, pairs, len(uncaught), applied))
     assert not uncaught, uncaught[:20]
     assert set(applied) == set(g.MUTATIONS), set(g.MUTATIONS) ^ set(applied)            # every mutation was planted somewhere
+
+
+# ------------------------------------------------------------------------------------------ 5. the 32-bit extent terms (FAR16)
+FAR16 = g.PATHS["FAR16"]
+
+
+def _far16_both(lib, r):
+    if r["kind"] == "tn":
+        wsb = g.tn_row_ws_bytes(r)
+        return _tn_row_export(lib, r, wsb), g.tn_row_query(r, wsb)
+    wsb = g.row_ws_bytes(r)
+    return _row_export(lib, r, wsb), g.row_query(r, wsb)
+
+
+def test_far16_limits_are_the_ones_the_source_states():
+    L = g.limits16()
+    assert L == dict(a_span=4.0e9, a_utt=2.0e9, a_ext=4.0e9, b_ext=4.0e9, pair_a_ext=4.0e9, pair_b_ext=4.0e9, span=4.0e9)
+
+
+def test_every_far16_row_matches_the_export_and_selects_what_it_names(lib, monkeypatch):
+    """the planner only tests pointers for alignment and NULL: both sides of every extent term are pinned through
+    lidbox_gemm_bf16_plan_query with fake pointers, no memory behind them"""
+    fast = set()
+    for r in FAR16:
+        _setenv(monkeypatch, r["env"])
+        got, want = _far16_both(lib, r)
+        assert got == want, (r["name"], got, want)
+        e = r["expect"]
+        assert (e["kernel"] is None or got[0] == e["kernel"]) and (e["not_kernel"] is None or got[0] != e["not_kernel"]), (r["name"], got)
+        if r["term"] == "gap":                                       # the K1-resident wgrad's covered-gap term at its own edge
+            cond = g.tn_kres_conditions(r["a"], r["b"], r["K1"], r["N"], g.plan_tn16_kres(r["M"], r["K1"], r["N"], r["env"]))
+            assert [k for k, v in cond.items() if not v] == ([] if r["zone"] == "edge-in" else ["gap_covered"]), (r["name"], cond)
+            continue
+        op, which = next(iter(r["far"].items()))
+        d = r["a"] if op == "A" else r.get("b")
+        if r["term"] in ("a_ext", "a_span"):
+            gq = g.a_ext16(r["a"], r["K"])
+        elif r["term"] == "a_utt":
+            gq = g.a_utt16(r["a"], r["K"])
+        elif r["term"] == "b_ext":
+            gq = g.b_ext16(r["N"], g.ldb_of(r), r["K"])
+        else:
+            gq = g.span16(d, r["K1"] if op == "A" else r["N"])
+        L = g.limits16()[r["term"]]
+        inside = r["zone"] in ("high", "edge-in")
+        assert (gq < L) == inside, (r["name"], gq)
+        if r["zone"] == "over":
+            assert gq >= gp.OVER * L
+        if r["zone"] == "high":
+            assert gq >= 0.975 * L, "a bf16 operand needs about 2e9 elements of extent"
+        if inside and r.get("twin_same", True):
+            fast.add(got[0])
+    assert fast >= {g.KS_DMA, g.KS_PP, g.KS_KRES0, g.KS_TN_PP, g.KS_TN_KRES}, fast
+
+
+def test_far16_sweep_term_by_term(lib, monkeypatch):
+    """each of batch_stride, rows_per_batch * row_stride and ldb stretched alone across each limit, in steps around it: the export
+    equals the restated plan at every step, and the kernel changes exactly where the term crosses its limit"""
+    n = 0
+    L = g.limits16()
+    for r in FAR16:
+        if r["zone"] != "edge-in" or not r["far"] or not r.get("twin_same", True):
+            continue
+        _setenv(monkeypatch, r["env"])
+        op, which = next(iter(r["far"].items()))
+        kernels = []
+        for k in (-(1 << 20), -64, -8, 0, 8, 64, 1 << 20, 1 << 27):
+            rr = dict(r)
+            if which == "ldb":
+                rr["ldb_pad"] = r["ldb_pad"] + k
+            elif which == "rpb":
+                kk = k // 8
+                rr["a"] = dict(r["a"], rpb=r["a"]["rpb"] + kk)
+                rr["M"] = rr["a"]["rpb"]
+                rr["c"] = gp._dense(rr["M"], r["N"])
+            else:
+                key = "a" if op == "A" else "b"
+                step = r[key]["rs"] if r["expect"]["kernel"] == g.KS_TN_KRES and op == "A" else 1
+                rr[key] = dict(r[key], bs=r[key]["bs"] + k * step)
+            got, want = _far16_both(lib, rr)
+            assert got == want, (r["name"], k, got, want)
+            kernels.append(got[0])
+            n += 1
+        assert all(k == r["expect"]["kernel"] for k in kernels[:4]) and all(k != r["expect"]["kernel"] for k in kernels[4:]), (r["name"], kernels)
+    # rows_per_batch * row_stride alone, through row_stride with batch = 1 (a_ext) and through rows_per_batch (a_span, a_utt above)
+    _setenv(monkeypatch, {})
+    for K, N, M in ((64, 64, 130),):
+        for zone in ("edge-in", "edge-out"):
+            rs = gp._solve(lambda s: g.a_ext16(dict(batch=1, rpb=M, rs=s, bs=0), K), L["a_ext"], zone, step=8, lo=K)
+            a, c = dict(batch=1, rpb=M, rs=rs, bs=0), gp._dense(M, N)
+            got = _export(lib, g.Q16S_NT, a, None, c, K, N, 0, 1 << 30, ldb=K)
+            assert got == g.plan_query(g.Q16S_NT, a, None, c, K, N, 0, {}, 1 << 30, ldb=K) and (got[0] == g.KS_DMA) == (zone == "edge-in"), (zone, got)
+            n += 1
+    print("%d planner queries around the limits" % n)
+    assert n >= 60
+
+
+def test_far16_pair_site_restated():
+    """pp2_problem's own a_ext / b_ext (no export reports it: the restated conditions, each limit failing alone)"""
+    for name, call, ok in g.far16_pair_calls():
+        cond = g.pp2_conditions(call, 2 * call["a"]["rpb"] * call["N"] * 4, {})
+        assert all(cond.values()) == ok and (ok or [k for k, v in cond.items() if not v] == ["ext"]), (name, cond)

@@ -365,3 +365,227 @@ def test_tn_emulation_inside_and_every_mutation_outside():
     assert not uncaught, uncaught
     assert {"drop_k_step", "drop_k_tail", "tail_not_zeroed", "col_shift_32", "row_from_0", "no_accum", "slab_twice", "slab_omitted",
             "bias_grad_slice_omitted"} <= applied
+
+
+# ------------------------------------------------------------------------------------------ 5. the 32-bit extent guards (FAR)
+FAR = gp.PATHS["FAR"]
+FAR_ROWS = [r for r in FAR if r["kind"] in ("nn", "nt")]
+FAR_TN = [r for r in FAR if r["kind"] == "tn"]
+
+
+def _first_kernel(r):
+    p = gp.far_tn_predict(r) if r["kind"] == "tn" else gp.far_row_predict(r)
+    return p, p["kernels"][0]
+
+
+def test_far_limits_are_the_ones_the_source_states():
+    """the limits are read from the source text; the rows below were built for these values, and a change of the .hip moves both"""
+    L = gp.limits()
+    assert (L["a_bytes"], L["b_bytes"], L["job_bytes"]) == (4.0e9, 4.0e9, 4.0e9) and (L["a_pad"], L["b_pad"]) == (64, 16.0)
+    assert (L["inner_rpb"], L["inner_rs"], L["inner_wrap"]) == (28, 1 << 25, 1 << 30)
+    assert L["a_bytes"] > 2 ** 31, "the fast kernels are allowed byte offsets with bit 31 set: what the FAR rows are there for"
+
+
+def test_every_far_row_lies_in_its_zone_of_the_guard():
+    n = 0
+    for r in FAR_ROWS + FAR_TN:
+        flop = 2.0 * r["M"] * r["N"] * (r["K1"] if r["kind"] == "tn" else r["K"])
+        assert flop <= 4.0e9, r["name"]
+        deref = gp.far_deref_bytes(r)
+        for op, which in r["far"].items():
+            if op == "C":
+                c, L = r["c"], gp.limits()
+                assert deref["C"] >= 4.5e9, (r["name"], deref)
+                wrap = c["bs"] - c["rpb"] * c["rs"] if c["batch"] > 1 else 0
+                want = {"wrap-edge-in": (wrap, L["inner_wrap"] - 4), "wrap-edge-out": (wrap, L["inner_wrap"]), "off0": (wrap, L["inner_wrap"] - 4),
+                        "rs-edge-in": (c["rs"], L["inner_rs"] - 4), "rs-edge-out": (c["rs"], L["inner_rs"])}[which]
+                assert want[0] == want[1], r["name"]
+                assert gp.store_inner_ok(c) == (not which.endswith("edge-out")), r["name"]
+                if which == "off0":                                 # every block inner and free of a boundary, the second utterance 2^32 bytes on
+                    assert c["rpb"] % 32 == 0 and c["bs"] * 4 >= 2 ** 32
+                if which.startswith("wrap"):                        # a boundary inside a 32-row block: the select form
+                    assert c["rpb"] % 32 != 0 and c["rpb"] >= L["inner_rpb"]
+                for o in ("A", "B"):                                # compact: no guard is near
+                    assert deref[o] < 2 ** 22
+                n += 1
+                continue
+            g, L = gp.far_guard(r, op)
+            step = lambda d: gp.far_guard(dict(r, **d), op)[0]
+            if op == "B":
+                nb = lambda k: step(dict(ldb_pad=r["ldb_pad"] + k))
+            else:
+                key = "a" if op in ("A", "X") else "b"
+                d0 = r[key]
+                nb = lambda k: step({key: dict(d0, bs=d0["bs"] + k) if which == "bs" else dict(d0, rs=d0["rs"] + k)})
+            zone = r["zone"]
+            if zone == "high":
+                assert g < L and deref[op] >= gp.HIGH_BYTES, (r["name"], g, deref)
+            elif zone == "edge-in":
+                assert g < L <= nb(4), r["name"]
+            elif zone == "edge-out":
+                assert nb(-4) < L <= g, r["name"]
+            else:
+                assert zone == "over" and g >= gp.OVER * L, r["name"]
+            n += 1
+    assert n == len(FAR_ROWS) + len(FAR_TN)
+    # SkOuterRows' int arithmetic: a_step = 16 rs >= 2^27 on a row-stride row, a_wrap >= 2^29 on a batch-stride row
+    hi = [r for r in FAR_TN if r["zone"] == "high"]
+    far_d = lambda r: r["a"] if "X" in r["far"] else r["b"]
+    assert any(16 * far_d(r)["rs"] >= 2 ** 27 for r in hi if "rs" in r["far"].values())
+    assert any(far_d(r)["bs"] - far_d(r)["rpb"] * far_d(r)["rs"] >= 2 ** 29 for r in hi if "bs" in r["far"].values())
+    for r in hi:                                                    # and they stay ints: the last offset plus one step or wrap
+        d = far_d(r)
+        assert gp.far_layout(d, 1).max() + max(16 * d["rs"], d["bs"] - d["rpb"] * d["rs"] if d["batch"] > 1 else 0) + 128 < 2 ** 31, r["name"]
+
+
+def test_every_far_row_selects_what_it_names_and_its_compact_twin_the_same():
+    seen = set()
+    for r in FAR_ROWS + FAR_TN:
+        p, k = _first_kernel(r)
+        e = r["expect"]
+        assert p["family"] == e["family"], (r["name"], p)
+        assert k.startswith("gemm_rows_dma_kernel" if e["kernel"] == "stream" else e["kernel"]), (r["name"], k)
+        if e.get("stream"):
+            assert p["g"] > 1, r["name"]
+        t = gp.compact_twin(r)
+        pt, kt = _first_kernel(t)
+        if r["zone"] in ("high", "edge-in", "c-far"):
+            assert (pt["family"], pt["kernels"], pt["launches"], pt.get("g"), pt["p"]) == (p["family"], p["kernels"], p["launches"], p.get("g"), p["p"]), r["name"]
+            seen.add(k.split("<")[0] + ("+stream" if p.get("g", 0) > 1 else ""))
+        else:
+            assert p["family"] == 0 and pt["family"] != 0, (r["name"], "a refusal falls to the register-staged kernels; its twin does not")
+    assert seen >= {"gemm_sk_rows_kernel", "gemm_skp_rows_kernel", "gemm_rows_dma_kernel", "gemm_rows_dma8_kernel", "gemm_rows_dma_kernel+stream",
+                    "gemm_sk_tn_kernel", "gemm_tn_dma_kernel", "gemm_rows_kernel"}, seen
+
+
+def test_far_pair_rows_refuse_one_predicate_each():
+    rows = [r for r in FAR if r["kind"] == "pair"]
+    assert sorted(r["refused"] for r in rows) == ["al_rows", "al_tn"]
+    for r in rows:
+        M, Co, N, K1 = r["M"], r["Co"], r["N"], r["K1"]
+        al_rows, al_tn = gp.pair_al(gp._dense(M, Co), Co, N, r["ldb"], r["x"], K1)
+        assert (al_rows, al_tn) == (r["refused"] != "al_rows", r["refused"] != "al_tn"), r["name"]
+        ws_nt, ws_tn = max(gp.rows_workspace(M, N, Co, {}), 2 * M * N * 4), gp.tn_workspace(M, K1, Co, {})
+        assert gp.pair_plan(M, Co, N, K1, ws_nt, ws_tn, {}) is not None, "the compact twin pairs"
+        assert gp.pair_plan(M, Co, N, K1, ws_nt, ws_tn, {}, al_rows, al_tn) is None, r["name"]
+
+
+def test_far_job_rows_stand_on_both_sides_of_the_limit_and_below_2_32():
+    rows = [r for r in FAR if r["kind"] == "job"]
+    assert {(r["splits"], r["bias_partials"], r["accumulate"]) for r in rows} == {(s, b, a) for s in (940, 960) for b in (False, True) for a in (0, 1)}
+    for r in rows:
+        g = gp.job_guard(r["splits"], r["n"])
+        assert (g < gp.limits()["job_bytes"]) == (r["zone"] == "high") and g < 2 ** 32 and (r["zone"] == "over" or g >= gp.HIGH_BYTES)
+        assert gp.reduce_job_vec_ok(0, r["splits"], r["n"] // r["N"], r["N"], 0, r["N"], r["bias_partials"]) == (r["zone"] == "high")
+
+
+def test_sparse_reference_and_judge_equal_the_flat_ones_on_small_rows():
+    rows = [r for r in ROWS if r["M"] and r["N"] and r["M"] * r["K"] < 1 << 16 and gp.row_predict(r)["kernels"]][::7][:14]
+    tns = [r for r in TN if r["M"] * r["K1"] < 1 << 16][:6]
+    assert len(rows) + len(tns) == 20
+    for r in rows:
+        for ds in ("normal", "exact"):
+            dat = gp.make_rows_data(r, ds)
+            assert np.array_equal(dat["a_flat"][gp.far_layout(r["a"], r["K"])[:, None] + np.arange(r["K"])], dat["A"], equal_nan=True)
+            p = gp.row_predict(r)["p"]
+            for mut in (None, "drop_k_step", "no_relu"):
+                flat = gp.emulate_rows(r["kind"], dat["A"], dat["B"], r["epi"], dat["bias"], dat["mask_flat"], dat["c_flat"], r["c"], 1, mut)
+                off = gp.far_layout(r["c"], r["N"])
+                got = flat[off[:, None] + np.arange(r["N"])]
+                changed = int((flat.view(np.int32) != gp.NAN_BITS).sum())
+                a, b = gp.judge_rows(r, ds, dat, flat, p), gp.judge_far_rows(r, ds, dat, got, changed, p)
+                assert a[0] == b[0] and (a[1] == b[1] or not a[0]), (r["name"], ds, mut, a, b)
+            flat = np.array(gp.emulate_rows(r["kind"], dat["A"], dat["B"], r["epi"], dat["bias"], dat["mask_flat"], dat["c_flat"], r["c"]))
+            gaps = np.ones(flat.size, bool)
+            gaps[gp.index(r["c"], r["N"]).ravel()] = False
+            if gaps.any():                                          # a gap word written: both judges refuse
+                flat[np.flatnonzero(gaps)[0]] = 1.0
+                got = flat[gp.far_layout(r["c"], r["N"])[:, None] + np.arange(r["N"])]
+                changed = int((flat.view(np.int32) != gp.NAN_BITS).sum())
+                assert not gp.judge_rows(r, ds, dat, flat, p)[0] and not gp.judge_far_rows(r, ds, dat, got, changed, p)[0], r["name"]
+    for r in tns:
+        dat = gp.make_tn_data(r, "normal")
+        for d, w, flat, dense in ((r["a"], r["K1"], dat["a_flat"], dat["A"]), (r["b"], r["N"], dat["b_flat"], dat["B"])):
+            assert np.array_equal(flat[gp.far_layout(d, w)[:, None] + np.arange(w)], dense, equal_nan=True), r["name"]
+
+
+def _far_operands(r):
+    """(operand, descriptor, columns) of the far operands of a row"""
+    out = []
+    for op in r["far"]:
+        if op == "A":
+            out.append((op, r["a"], r["K"]))
+        elif op == "B":
+            rows, cols = (r["K"], r["N"]) if r["kind"] == "nn" else (r["N"], r["K"])
+            out.append((op, dict(batch=1, rpb=rows, rs=gp.ldb_of(r), bs=0), cols))
+        elif op == "C":
+            out.append((op, r["c"], r["N"]))
+            if r["epi"] in gp.EPI_HAS_MASK:
+                out.append(("mask", r["c"], r["N"]))
+        elif op == "X":
+            out.append((op, r["a"], r["K1"]))
+        elif op == "dY":
+            out.append((op, r["b"], r["N"]))
+    return out
+
+
+def _verdict_under_mistake(r, op, d, cols, mut, dat, pred):
+    """(applies, caught, rows that left the allocation, message) for one planted addressing mistake on one far operand"""
+    bad = gp.mistaken_offsets(mut, d, cols)
+    if bad is None:
+        return False, True, 0, ""
+    f32 = lambda x: np.asarray(x, np.float32)
+    if r["kind"] == "tn":
+        dd = dict(dat)
+        key = "A" if op == "X" else "B"
+        dd[key], left = gp.emulate_far_gather(d, cols, dat[key], bad)
+        v, S, g, Sg = gp.tn_reference(r, dict(dat, A=dd["A"], B=dd["B"]))
+        got_c = np.array(dat["c_flat"], np.float32)
+        got_c[:, :r["N"]] = f32(v)
+        ok = gp.judge_tn(r, "normal", dat, got_c, f32(g), pred["splits"], pred["rps"])[0]
+    else:
+        A, B, mask, old = dat["A"], dat["B"], dat["mask"], dat["old"]
+        left = 0
+        if op == "A":
+            A, left = gp.emulate_far_gather(d, cols, A, bad)
+        elif op == "B":
+            B, left = gp.emulate_far_gather(d, cols, B, bad)
+        elif op == "mask":
+            mask, left = gp.emulate_far_gather(d, cols, mask, bad)
+        if op == "C" and old is not None:                          # the old values are read through the same mistaken address
+            old_read, _ = gp.emulate_far_gather(d, cols, old, bad)
+        else:
+            old_read = old
+        res = f32(gp.rows_reference(r["kind"], A, B, r["epi"], dat["bias"], mask, old_read)[0])
+        changed = r["M"] * r["N"]
+        if op == "C":
+            res, changed, left = gp.emulate_far_scatter(d, cols, res, bad, old)
+        ok = gp.judge_far_rows(r, "normal", dat, res, changed, pred["p"])[0]
+    return True, not ok, left, "%s: %s of %s not caught" % (r["name"], mut, op)
+
+
+def test_every_planted_addressing_mistake_becomes_a_wrong_number_inside_the_allocation():
+    """the buffer layout of tests/far_buffers.py ([2^31 + 256 bytes][extent][256 bytes], NaN everywhere but the payload): each
+    addressing mistake, planted in an emulated gather (inputs) or scatter (C), is rejected by the judge on every row it can change,
+    and no mistaken row leaves the allocation"""
+    pairs, uncaught, seen = 0, [], set()
+    for r in FAR_ROWS + FAR_TN:
+        if r["zone"] not in ("high", "edge-in", "c-far") or (r["kind"] != "tn" and r["M"] * r["K"] > 1 << 18 and "A" not in r["far"]):
+            continue
+        t = gp.compact_twin(r)
+        dat = gp.make_tn_data(t, "normal") if r["kind"] == "tn" else gp.make_rows_data(t, "normal")
+        pred = gp.far_tn_predict(r) if r["kind"] == "tn" else gp.far_row_predict(r)
+        for op, d, cols in _far_operands(r):
+            for mut in gp.ADDRESSING_MISTAKES:
+                applies, caught, left, msg = _verdict_under_mistake(r, op, d, cols, mut, dat, pred)
+                if not applies:
+                    continue
+                pairs += 1
+                seen.add(mut)
+                assert left == 0, "%s: %s of %s leaves the allocation (%d rows)" % (r["name"], mut, op, left)
+                if not caught:
+                    uncaught.append(msg)
+    print("%d (row, operand, mistake) pairs, mistakes met: %s" % (pairs, sorted(seen)))
+    assert not uncaught, uncaught
+    # element_offset_mod_2^31 needs an element offset of 2^31 (8.6 GB behind the base): beyond the rows' 32 GiB budget, it changes none
+    assert seen == set(gp.ADDRESSING_MISTAKES) - {"element_offset_mod_2^31"} and pairs >= 60
