@@ -901,7 +901,7 @@ int lidbox_gru_fwd(const float* U0, const float* U1, const float* b_rec0, const 
 int lidbox_gru_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg, const float* hseq, float* qh,
                    const float* dh_seq, long dh_batch_stride, const float* dh_last, void* workspace, size_t workspace_bytes,
                    lidbox_stream_t stream);
-/* ------------------------------------------------------------------ ragged recurrence, forward only (csrc/rnn_ragged.hip)
+/* ------------------------------------------------------------------ ragged recurrence, forward only (csrc/lstm_step.hip, gru.hip, rnn.hip)
  * lidbox_lstm_step_fwd / lidbox_gru_fwd for B utterances of DIFFERENT lengths T_b >= 1 in one walk of max T_b steps (inference;
  * no reference counterpart: the Keras layers run without masking, so a padded batch is a different computation).  The dense
  * [B][T+2] convention with a per-utterance T: utterance b owns the rows seg[b] .. seg[b+1] = seg[b] + T_b + 2 of every

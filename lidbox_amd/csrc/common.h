@@ -25,14 +25,17 @@ void lidbox_set_error(const char* fmt, ...);
         }                                                                               \
     } while (0)
 
-#define LBX_LAUNCH_OK()                                                                 \
+// fn: the entry point a helper launches for
+#define LBX_LAUNCH_OK_AS(fn)                                                            \
     do {                                                                                \
         hipError_t e__ = hipGetLastError();                                             \
         if (e__ != hipSuccess) {                                                        \
-            lidbox_set_error("%s: kernel launch failed: %s", __func__, hipGetErrorString(e__)); \
+            lidbox_set_error("%s: kernel launch failed: %s", fn, hipGetErrorString(e__)); \
             return LIDBOX_E_LAUNCH;                                                     \
         }                                                                               \
     } while (0)
+
+#define LBX_LAUNCH_OK() LBX_LAUNCH_OK_AS(__func__)
 
 static inline long lbx_cdiv(long a, long b) { return (a + b - 1) / b; }
 

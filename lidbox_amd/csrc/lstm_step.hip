@@ -25,6 +25,9 @@
 // stride to be a multiple of its width and the pointers aligned to it.  Backward's K axis is 4H long and both operands'
 // rows are 4H floats apart, so its float4 path needs only 16-byte aligned pointers.
 //
+// The forward kernel is a template over a row map (rnn_step.h: DenseRows for the buffers above, RaggedRows for utterances of
+// different lengths in one walk, lidbox_lstm_ragged_fwd; layout and walk are described there).
+//
 // No inter-workgroup communication, no atomics, no spin-waits: steps are ordered by the stream alone.  Every output element
 // is one MFMA k-chain over its own row, in an order that depends on neither B nor the row's place in the batch, so a
 // row's results are bit-identical whatever the batch.
@@ -37,6 +40,7 @@
 
 namespace {
 
+// backward's arguments (hseq and h_rs are forward's: unused)
 struct StepArgs {
     const float* U[2];
     float* zg;
@@ -50,39 +54,52 @@ struct StepArgs {
     int B, T, H, dirs;
 };
 
-// one forward step s of both directions (direction d: t = s forward, T-1-s reverse)
-template <int VW>
-__global__ __launch_bounds__(256) void lstm_step_fwd_kernel(const StepArgs a, int s) {
+// forward's arguments; where a row lives is the map's business (rnn_step.h)
+template <typename Rows>
+struct FwdArgs {
+    const float* U[2];
+    float* zg;
+    float* hseq;
+    long h_rs;
+    float* cseq;
+    float* hlast;                // may be NULL
+    Rows rows;
+    int H, dirs;
+};
+
+// one forward step s of both directions over the slots 0 .. n-1 (direction d: t = s forward, T-1-s reverse)
+template <int VW, typename Rows>
+__global__ __launch_bounds__(256) void lstm_step_fwd_kernel(const FwdArgs<Rows> a, int s, int n) {
     __shared__ __attribute__((aligned(16))) float Bs[LstmStep::KCF * STEP_LDF<LstmStep>];
-    const int H = a.H, T = a.T, B = a.B, d = blockIdx.z, H4 = 4 * H;
+    const int H = a.H, d = blockIdx.z, H4 = 4 * H;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int u0 = blockIdx.y * STEP_UNITS;
-    const int t = d == 0 ? s : T - 1 - s;
-    const int prow = d == 0 ? t : t + 2;                      // hseq row of h_{t-1} (forward) / h_{t+1} (reverse)
+    const long nb = d == 0 ? -1 : 1;                          // the neighbour state's row: h_{t-1} (forward) / h_{t+1} (reverse)
     const int rb = blockIdx.x * STEP_ROWS + w * 16;
     // the cell's own operands (the step's slice of zg, c_{t-1}) do not depend on the product: they are fetched first, so that
-    // their trip to HBM runs under it.  Lane (c, g) holds unit u0 + c of rows rb + 4g + i (the 16x16 C/D map: col = lane & 15,
-    // row = 4 (lane >> 4) + i).
+    // their trip to HBM runs under it.  Lane (c, g) holds unit u0 + c of the slots rb + 4g + i (the 16x16 C/D map:
+    // col = lane & 15, row = 4 (lane >> 4) + i).
     const int u = u0 + (lane & 15);
-    const int tp = d == 0 ? t - 1 : t + 1;
+    typename Rows::At at[4];
     float xz[4][4], cprev[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int b = rb + 4 * (lane >> 4) + i;
-        const bool ok = u < H && b < B;
-        const size_t row = ((size_t)d * B + (ok ? b : 0)) * T;
-        const float* gz = a.zg + (row + t) * H4 + (ok ? u : 0);
+        const int j = rb + 4 * (lane >> 4) + i;
+        const bool ok = u < H && j < n;
+        at[i] = a.rows.at(ok ? j : 0, d, s);
+        const size_t row = a.rows.frame(at[i], d, s);
+        const float* gz = a.zg + row * H4 + (ok ? u : 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) xz[q][i] = ok ? gz[q * H] : 0.0f;
-        cprev[i] = ok && s > 0 ? a.cseq[(row + tp) * H + u] : 0.0f;
+        cprev[i] = ok && s > 0 ? a.cseq[(row + nb) * H + u] : 0.0f;
     }
     f32x4 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (s > 0) {                                              // h_{-1} = 0: the first step's product is skipped
-        const int ra = rb + (lane & 15);
-        const bool aok = ra < B;
-        const float* arow = a.hseq + ((size_t)(aok ? ra : 0) * (T + 2) + prow) * a.h_rs + d * H;
+        const int ja = rb + (lane & 15);
+        const bool aok = ja < n;
+        const float* arow = a.hseq + (a.rows.hrow(a.rows.at(aok ? ja : 0, d, s), d, s) + nb) * a.h_rs + d * H;
         const float* U = a.U[d];
         for (int kc = 0; kc < H; kc += LstmStep::KCF) {
             const int klen = min(LstmStep::KCF, H - kc), kpad = (klen + 31) & ~31;
@@ -97,10 +114,11 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(const StepArgs a, in
     if (u >= H) return;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int b = rb + 4 * (lane >> 4) + i;
-        if (b >= B) continue;
-        const size_t row = ((size_t)d * B + b) * T;
-        float* gz = a.zg + (row + t) * H4 + u;
+        const int j = rb + 4 * (lane >> 4) + i;
+        if (j >= n) continue;
+        const typename Rows::At ai = Rows::LOOKUP ? at[i] : a.rows.at(j, d, s);
+        const size_t row = a.rows.frame(ai, d, s);
+        float* gz = a.zg + row * H4 + u;
         const float ig = sigm(xz[0][i] + acc[0][i]), fg = sigm(xz[1][i] + acc[1][i]);
         const float gg = tanhf(xz[2][i] + acc[2][i]), og = sigm(xz[3][i] + acc[3][i]);
         const float c = fg * cprev[i] + ig * gg;
@@ -108,8 +126,11 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(const StepArgs a, in
         gz[H] = fg;
         gz[2 * H] = gg;
         gz[3 * H] = og;
-        a.cseq[(row + t) * H + u] = c;
-        a.hseq[((size_t)b * (T + 2) + t + 1) * a.h_rs + d * H + u] = og * tanhf(c);
+        a.cseq[row * H + u] = c;
+        const float h = og * tanhf(c);                        // behind the stores it does not feed: they leave under it
+        a.hseq[a.rows.hrow(ai, d, s) * a.h_rs + d * H + u] = h;
+        if (a.hlast && a.rows.last(j, s))                     // the direction's final h: t = T - 1 forward, t = 0 reverse
+            a.hlast[a.rows.out(j) * (a.dirs * H) + d * H + u] = h;
     }
 }
 
@@ -187,6 +208,24 @@ inline int fwd_width(int H, long h_rs, const void* U0, const void* U1, const voi
     return 1;
 }
 
+// the forward walk: T steps, step s over the running(s) slots still in it
+template <typename Rows, typename Running>
+int walk_fwd(const char* fn, const FwdArgs<Rows>& a, int T, Running running, hipStream_t st) {
+    const int vw = fwd_width(a.H, a.h_rs, a.U[0], a.U[1], a.hseq);
+    for (int s = 0; s < T; ++s) {
+        const int n = running(s);
+        const dim3 grid = step_grid(n, a.H, a.dirs);
+        if (vw == 4)
+            hipLaunchKernelGGL((lstm_step_fwd_kernel<4, Rows>), grid, dim3(256), 0, st, a, s, n);
+        else if (vw == 2)
+            hipLaunchKernelGGL((lstm_step_fwd_kernel<2, Rows>), grid, dim3(256), 0, st, a, s, n);
+        else
+            hipLaunchKernelGGL((lstm_step_fwd_kernel<1, Rows>), grid, dim3(256), 0, st, a, s, n);
+        LBX_LAUNCH_OK_AS(fn);
+    }
+    return LIDBOX_OK;
+}
+
 }  // namespace
 
 extern "C" size_t lidbox_lstm_step_workspace(int B, int T, int H, int dirs) {
@@ -203,20 +242,20 @@ extern "C" int lidbox_lstm_step_fwd(const float* U0, const float* U1, int dirs, 
     if (B == 0) return LIDBOX_OK;
     (void)workspace;                                          // forward carries nothing between steps
     (void)workspace_bytes;
-    StepArgs a{{U0, dirs == 2 ? U1 : U0}, zg, hseq, h_row_stride, cseq, nullptr, 0, 0, nullptr, nullptr, B, T, H, dirs};
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid = step_grid(B, H, dirs);
-    const int vw = fwd_width(H, h_row_stride, a.U[0], a.U[1], hseq);
-    for (int s = 0; s < T; ++s) {
-        if (vw == 4)
-            hipLaunchKernelGGL(lstm_step_fwd_kernel<4>, grid, dim3(256), 0, st, a, s);
-        else if (vw == 2)
-            hipLaunchKernelGGL(lstm_step_fwd_kernel<2>, grid, dim3(256), 0, st, a, s);
-        else
-            hipLaunchKernelGGL(lstm_step_fwd_kernel<1>, grid, dim3(256), 0, st, a, s);
-        LBX_LAUNCH_OK();
-    }
-    return LIDBOX_OK;
+    const FwdArgs<DenseRows> a{{U0, dirs == 2 ? U1 : U0}, zg, hseq, h_row_stride, cseq, nullptr, {B, T}, H, dirs};
+    return walk_fwd(__func__, a, T, [B](int) { return B; }, (hipStream_t)stream);
+}
+
+extern "C" int lidbox_lstm_ragged_fwd(const float* U0, const float* U1, int dirs, int B, int H, long rows, const long* slots,
+                                      const long* sorted_lengths, float* zg, float* hseq, long h_row_stride, float* cseq,
+                                      float* hlast, lidbox_stream_t stream) {
+    if (int e = check_step_args(__func__, 4, U0, U1, dirs, B, 1, H)) return e;
+    if (B == 0) return LIDBOX_OK;
+    if (int e = check_ragged_args(__func__, 4, dirs, B, H, rows, slots, sorted_lengths, zg, hseq, cseq, h_row_stride)) return e;
+    const FwdArgs<RaggedRows> a{{U0, dirs == 2 ? U1 : U0}, zg, hseq, h_row_stride, cseq, hlast, {slots, rows, B}, H, dirs};
+    int n = B;
+    return walk_fwd(__func__, a, (int)sorted_lengths[0], [&](int s) { return n = running(sorted_lengths, n, s); },
+                    (hipStream_t)stream);
 }
 
 extern "C" int lidbox_lstm_step_bwd(const float* U0, const float* U1, int dirs, int B, int T, int H, float* zg,

@@ -347,6 +347,36 @@ __global__ __launch_bounds__(256) void seq_avg_pool_bwd_kernel(const float* __re
     *p = accumulate ? *p + g : g;
 }
 
+// the same over utterances of different lengths, forward only: out[b, c] (ldo floats between rows) = alpha * mean over the
+// lengths[b] rows from row first_rows[b] of x, in the summation order of ragged.hip's pools for EVERY length: 256 threads =
+// 16 channels x 16 time groups; per group the rows g, g + 16, .. in order, then the 16 groups in order, / T, * alpha.
+// Grid (ceil(C / 16), utterance blocks), utterances grid-strided.
+__global__ __launch_bounds__(256) void seq_avg_pool_ragged_kernel(const float* __restrict__ x, long rs,
+                                                                  const long* __restrict__ first_rows,
+                                                                  const long* __restrict__ lengths, long B, int C, float alpha,
+                                                                  float* __restrict__ out, long ldo) {
+    __shared__ float red[16][17];
+    const int cg = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + cg;
+    const bool active = c < C;
+    for (long b = blockIdx.y; b < B; b += gridDim.y) {
+        const long T = lengths[b];
+        const float* xp = x + first_rows[b] * rs + c;
+        float sum = 0.f;
+        if (active)
+            for (long t = g; t < T; t += 16) sum += xp[t * rs];
+        red[g][cg] = sum;
+        __syncthreads();
+        if (active && g == 0) {
+            float m = 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) m += red[k][cg];
+            out[b * ldo + c] = alpha * (m / (float)T);
+        }
+        __syncthreads();                                     // the next utterance writes red
+    }
+}
+
 int pick_rt(int B, int dirs) {
     // fewest rows per workgroup that still fit one wave of workgroups on the 256 CUs: the walk through time is latency-bound
     for (int rt = 1; rt < 4; rt *= 2)
@@ -503,6 +533,18 @@ extern "C" int lidbox_seq_avg_pool_fwd(const float* x, int B, int T, int C, long
     if (B == 0) return LIDBOX_OK;
     hipLaunchKernelGGL(seq_avg_pool_fwd_kernel, dim3((unsigned)lbx_cdiv((long)B * C, 256)), dim3(256), 0, (hipStream_t)stream,
                        x, B, T, C, batch_stride, row_stride, alpha, out, ldo);
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_seq_avg_pool_ragged_fwd(const float* x, long row_stride, const long* first_rows, const long* lengths, long B,
+                                              int C, float alpha, float* out, long ldo, lidbox_stream_t stream) {
+    LBX_ARG(x && first_rows && lengths && out, "x, first_rows, lengths, out != NULL");
+    LBX_ARG(B >= 0 && C >= 1 && row_stride >= C && ldo >= C, "B >= 0; C >= 1; row_stride >= C; ldo >= C");
+    if (B == 0) return LIDBOX_OK;
+    const unsigned by = (unsigned)(B > 8192 ? 8192 : B);      // the loop over utterances strides past it
+    hipLaunchKernelGGL(seq_avg_pool_ragged_kernel, dim3((unsigned)lbx_cdiv(C, 16), by), dim3(256), 0, (hipStream_t)stream, x,
+                       row_stride, first_rows, lengths, B, C, alpha, out, ldo);
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

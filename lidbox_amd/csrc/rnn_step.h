@@ -12,7 +12,12 @@
 //
 // What differs between the two recurrences is a parameter set (GruStep, LstmStep) and the kernels themselves: the cell,
 // which of its operands are fetched ahead of the product, and where the first A trip of a chunk is issued.
+//
+// At the end: the row maps (DenseRows, RaggedRows) through which one forward kernel per recurrence serves the dense and the
+// ragged walk, and the host checks of the ragged entry points (check_ragged_args, running).
 #pragma once
+
+#include <stdint.h>
 
 #include "common.h"
 #include "rnn_cell.h"
@@ -237,6 +242,96 @@ inline bool aligned_to(unsigned bytes, Ptr... p) {
 
 inline dim3 step_grid(int B, int H, int dirs) {
     return dim3((unsigned)lbx_cdiv(B, STEP_ROWS), (unsigned)lbx_cdiv(H, STEP_UNITS), (unsigned)dirs);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- row maps
+// Where a row lives is all that differs between a forward walk over a dense batch and one over utterances of DIFFERENT
+// lengths (forward only, inference; no reference counterpart: tf.data batches need one shape, and the Keras layers run
+// without masking, so a padded batch starts every reverse direction inside the padding).  The forward kernels ask a map.
+//
+// Dense: zg / cseq / qh [dirs][B][T], hseq [B][T+2] with frame t at row t+1 and zero rows 0 and T+1, hlast [B].
+//
+// Ragged (the dense [B][T+2] convention with a per-utterance T; lidbox_hip.h has the buffers): utterance b with T_b frames owns
+// the rows seg[b] .. seg[b+1] = seg[b] + T_b + 2 of every per-frame buffer of the layer.  Row seg[b] is a pad row, frame t sits at
+// row seg[b] + 1 + t, row seg[b+1] - 1 is a pad row.  One row index serves hseq [rows][h_row_stride], zg [dirs][rows][NG H] and
+// cseq / qh [dirs][rows][H], so a layer's input projection is ONE GEMM over all rows (the pad rows of zg receive the bias and are
+// never read) and no utterance is ever moved in memory.
+//
+// The walk: step s = 0 .. T_max - 1 is one launch for both directions, over the n_s = #{b : T_b > s} utterances still running
+// (dense: all B, every step).  Slot j of a ragged step is the j-th longest utterance (stable sort by length, descending), so the
+// running ones are the slots 0 .. n_s - 1 of a device table `slots` [3][B] = (first row seg[b], length T_b, utterance index b);
+// a dense slot is the batch row.  Grid = ceil(n_s / 64) x ceil(H / 16) x dirs: later ragged steps launch fewer row tiles.
+// Direction 0 works on t = s, direction 1 on t = T_b - 1 - s.  In both layouts the neighbour state sits one row in front of
+// (direction 0) resp. behind (direction 1) the frame's own row, in hseq and in cseq alike; in a ragged buffer that is inside the
+// utterance's own segment.  The first step of a direction skips the product (h_{-1} = 0) and reads no neighbour.
+//
+// Every output element is one MFMA k-chain over its own row, so every utterance's gates, c / qh, h and hlast of a ragged walk
+// are bit for bit what the dense walk gives it at B = 1, T = T_b, whatever its neighbours, its place in the batch and its slot.
+//
+// A kernel asks `at(j, d, s)` for a slot's At and the other members for its rows.  A ragged At is the frame's row, looked up in
+// `slots`: LOOKUP tells a kernel that prefetches to keep it over the product, so that the dependent load runs under the product
+// and not in front of the stores (0.9 us per step of the LSTM, LAB_NOTEBOOK section 32).  A dense At is the batch row itself,
+// cheaper to form again than to keep in a kernel at the register limit.
+struct DenseRows {
+    int B, T;
+    typedef int At;              // the batch row
+    static constexpr bool LOOKUP = false;
+    __device__ __forceinline__ At at(int j, int, int) const { return j; }
+    __device__ __forceinline__ int t(int d, int s) const { return d == 0 ? s : T - 1 - s; }
+    // row of the frame in zg / cseq / qh, and in hseq
+    __device__ __forceinline__ size_t frame(At b, int d, int s) const { return ((size_t)d * B + b) * T + t(d, s); }
+    __device__ __forceinline__ size_t hrow(At b, int d, int s) const { return (size_t)b * (T + 2) + t(d, s) + 1; }
+    // is s the last step of slot j (t = T - 1 forward, t = 0 reverse), and its row of hlast
+    __device__ __forceinline__ bool last(int, int s) const { return s == T - 1; }
+    __device__ __forceinline__ size_t out(int j) const { return j; }
+};
+
+struct RaggedRows {
+    const long* slots;           // [3][B]: first row, length, utterance index of slot j
+    long rows;                   // rows per direction of zg and cseq / qh
+    int B;
+    typedef long At;             // the frame's row within a direction
+    static constexpr bool LOOKUP = true;
+    __device__ __forceinline__ At at(int j, int d, int s) const {
+        return slots[j] + 1 + (d == 0 ? (long)s : slots[B + j] - 1 - s);
+    }
+    __device__ __forceinline__ size_t frame(At r, int d, int) const { return (size_t)d * rows + r; }
+    __device__ __forceinline__ size_t hrow(At r, int, int) const { return r; }
+    __device__ __forceinline__ bool last(int j, int s) const { return slots[B + j] == s + 1; }
+    __device__ __forceinline__ size_t out(int j) const { return slots[2 * B + j]; }
+};
+
+// what a ragged walk asks of its arguments beyond check_step_args (B >= 1 here); ng: gates
+inline int check_ragged_args(const char* fn, int ng, int dirs, int B, int H, long rows, const long* slots,
+                             const long* sorted_lengths, const float* zg, const float* hseq, const float* aux, long h_rs) {
+    if (!(slots && sorted_lengths && zg && hseq && aux)) {
+        lidbox_set_error("%s: invalid argument: slots, sorted_lengths, zg, hseq and %s != NULL", fn, ng == 4 ? "cseq" : "qh");
+        return LIDBOX_E_INVALID;
+    }
+    if (h_rs < (long)dirs * H) {
+        lidbox_set_error("%s: invalid argument: h_row_stride >= dirs * H", fn);
+        return LIDBOX_E_INVALID;
+    }
+    long total = 0;
+    for (int j = 0; j < B; ++j) {
+        if (sorted_lengths[j] < 1 || (j > 0 && sorted_lengths[j] > sorted_lengths[j - 1]) || sorted_lengths[j] > INT32_MAX - 2) {
+            lidbox_set_error("%s: invalid argument: sorted_lengths must be >= 1 and non-increasing (entry %d is %ld)", fn, j,
+                             sorted_lengths[j]);
+            return LIDBOX_E_INVALID;
+        }
+        total += sorted_lengths[j];
+    }
+    if (rows < total + 2L * B || rows > (1L << 40) / ((long)ng * H)) {
+        lidbox_set_error("%s: invalid argument: rows >= sum of lengths + 2 B (%ld), rows * %dH <= 2^40", fn, total + 2L * B, ng);
+        return LIDBOX_E_INVALID;
+    }
+    return LIDBOX_OK;
+}
+
+// the slots of a ragged walk still running at step s, of the n that ran the step before: sorted_lengths is non-increasing
+inline int running(const long* sorted_lengths, int n, int s) {
+    while (n > 0 && sorted_lengths[n - 1] <= s) --n;
+    return n;
 }
 
 }  // namespace

@@ -23,7 +23,7 @@ so conv i is one GEMM over M_{i+1} - p_{i+1} rows.  It also writes the p_{i+1} p
 behind the GEMM) and the slack rows, which no valid output row ever reads: the last frame's window ends at padded position
 (T_{i+1,b} - 1) s_i + k_i - 1 <= p_i + T_{i,b} - 1.  The last GEMM rows read up to k_i - 1 rows behind M_i, which the buffers have.
 
-`recurrent_plan` is the plan of the ragged RECURRENT pass (csrc/rnn_ragged.hip): the dense [B][T + 2] convention of the recurrence
+`recurrent_plan` is the plan of the ragged RECURRENT pass (csrc/rnn_step.h: RaggedRows): the dense [B][T + 2] convention of the recurrence
 kernels with a per-utterance T.  Utterance b owns the rows seg[b] .. seg[b + 1] of every per-frame buffer of a layer, seg[b] =
 row_offsets[b] + 2 b: a pad row, its T_b frames, a pad row; Rp = total_T + 2 B rows in all.  The walk through time runs step s over
 the n_s = #{b : T_b > s} utterances that are still running; slot j of a step is the j-th longest utterance under a stable sort by

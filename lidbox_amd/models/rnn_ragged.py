@@ -4,8 +4,8 @@ under its Conv2D blocks `conv_rnn.ConvRecurrentModel`): the recurrent specialisa
 inference on B utterances of DIFFERENT lengths in one pass:
 
     lidbox_ragged_pack_rows (pad = 1)  ->  per layer and direction ONE input projection GEMM over all Rp rows  ->
-    lidbox_lstm_ragged_fwd / lidbox_gru_ragged_fwd (csrc/rnn_ragged.hip: T_max launches, each over the utterances still
-    running)  ->  the model's head on each utterance's own frames or final states
+    lidbox_lstm_ragged_fwd / lidbox_gru_ragged_fwd (csrc/lstm_step.hip, gru.hip: the dense forward step kernels over a
+    ragged row map, T_max launches, each over the utterances still running)  ->  the model's head on each utterance's own frames or final states
 
 in the layout of `ragged.recurrent_plan`.  Every utterance gets what the dense pass gives it alone: the reverse directions start
 at its own last frame, time averages run over its own frames, "the final h" is the state after its own last frame -- none of

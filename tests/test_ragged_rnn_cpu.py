@@ -1,9 +1,11 @@
 """
 Host side of the ragged recurrent pass (no GPU): `models.ragged.recurrent_plan` against a brute-force restatement of its
-definition, its refusal of empty utterances, and the presence of the new entry points in the header and the ctypes table.
+definition, its refusal of empty utterances, the presence of the new entry points in the header and the ctypes table, and the
+instantiations of the forward step kernels that the dense and the ragged walk share.
 """
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -78,6 +80,47 @@ def test_new_symbols_are_declared_and_bound():
         assert re.search(r"\b%s\s*\(" % name, header), name
         assert name in nv._SIGS and hasattr(nv.lib, name), name
     assert len(nv._SIGS["lidbox_lstm_ragged_fwd"][1]) == 14 and len(nv._SIGS["lidbox_gru_ragged_fwd"][1]) == 15
+
+
+def _resource_usage(build, tmp_path, name):
+    """{function name: {remark field: number}} of one source compiled for gfx950 with the flags of the build"""
+    cmd = [build.HIPCC] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, name + ".hip"),
+                                         "-o", str(tmp_path / (name + ".o"))]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "--offload-arch=gfx950" in cmd
+    usage, fn = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            fn = m.group(1)
+        m = re.search(r"remark: .*?(ScratchSize|LDS Size) \[bytes/\w+\]: (\d+)", line)
+        if m and fn:
+            usage.setdefault(fn, {})[m.group(1)] = int(m.group(2))
+    return usage
+
+
+def test_one_forward_kernel_per_recurrence_serves_both_layouts(tmp_path):
+    """lstm_step_fwd_kernel<VW, Rows> and gru_fwd_step_kernel<VEC, Rows> exist for every load path x {DenseRows, RaggedRows},
+    nothing in either file uses scratch, a dense and a ragged instantiation of one load path have the same LDS size, and
+    no copy named *_ragged_fwd_kernel is left.  Itanium names: <length><name>I <args> E, Li<n>E an int, Lb<0|1>E a bool."""
+    from lidbox_amd import build
+    for src, kernel, arg, paths in (("lstm_step", "lstm_step_fwd_kernel", "Li", {4, 2, 1}),
+                                    ("gru", "gru_fwd_step_kernel", "Lb", {1, 0})):
+        usage = _resource_usage(build, tmp_path, src)
+        assert usage and all(set(u) == {"ScratchSize", "LDS Size"} for u in usage.values()), usage
+        assert all(u["ScratchSize"] == 0 for u in usage.values()), usage
+        assert not [k for k in usage if "_ragged_fwd_kernel" in k], sorted(usage)
+        lds = {}
+        for k, u in usage.items():
+            m = re.search(r"\d+%sI%s(\d+)E.*?\d+(DenseRows|RaggedRows)E" % (kernel, arg), k)
+            if m:
+                assert (int(m.group(1)), m.group(2)) not in lds, k
+                lds[int(m.group(1)), m.group(2)] = u["LDS Size"]
+        assert set(lds) == {(p, rows) for p in paths for rows in ("DenseRows", "RaggedRows")}, sorted(usage)
+        assert all(lds[p, "DenseRows"] == lds[p, "RaggedRows"] > 0 for p in paths), lds
+        # the forward kernel exists under no other template signature
+        assert sum(1 for k in usage if kernel in k) == len(lds), sorted(usage)
 
 
 def test_models_have_the_methods_the_pipeline_looks_up():

@@ -1,6 +1,6 @@
 """
-The ragged recurrent pass on the device: the walks of csrc/rnn_ragged.hip through the C ABI, then forward_ragged / predict_ragged /
-embed_ragged of lstm, ap_lstm, bi_gru and spherespeaker, steps.extract_embeddings(ragged: true) and util.predict_ragged_with_model.
+The ragged recurrent pass on the device: the ragged walks of csrc/lstm_step.hip and gru.hip (the dense forward step kernels over
+rnn_step.h's RaggedRows) and the ragged pool of rnn.hip through the C ABI, then forward_ragged / predict_ragged / embed_ragged of lstm, ap_lstm, bi_gru and spherespeaker, steps.extract_embeddings(ragged: true) and util.predict_ragged_with_model.
 
 Kernel level.  Every buffer a call may write is a tests/guarded.py payload: NaN around it, NaN wherever the kernel must write (the
 frame rows of hseq's slice, of cseq / qh, all of hlast), zero on the pad rows of hseq's slice, recognisable finite values on the
