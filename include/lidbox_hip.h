@@ -1064,7 +1064,7 @@ int lidbox_seq_avg_pool_bwd(const float* dout, long ldo, int B, int T, int C, fl
 int lidbox_mla_attention_fwd(const float* z, int B, int T, int K, float* att, long ld_att, float* colsum, lidbox_stream_t stream);
 int lidbox_mla_attention_bwd(const float* z, const float* att, long ld_att, const float* colsum, const float* datt, long ld_datt,
                              int B, int T, int K, float* dz, lidbox_stream_t stream);
-/* lidbox_mla_attention_fwd on B utterances of different lengths that lie end to end (inference: there is no ragged backward):
+/* lidbox_mla_attention_fwd on B utterances of different lengths that lie end to end (its backward: lidbox_mla_attention_ragged_bwd):
  *   z            [total_T][K]: utterance b owns the rows row_offsets[b] .. row_offsets[b + 1]
  *   row_offsets  device int64 [B + 1], rising from 0.  Every utterance has at least one row and fewer than 2^31; the kernel
  *                trusts both, as lidbox_stats_pool_ragged_fwd trusts lengths[b] >= 1
@@ -1077,6 +1077,21 @@ int lidbox_mla_attention_bwd(const float* z, const float* att, long ld_att, cons
  * No atomics, no communication between workgroups.  1 <= K <= 1024; B == 0 returns without a launch. */
 int lidbox_mla_attention_ragged_fwd(const float* z, const long* row_offsets, long B, int K, float* att, long ld_att, float* colsum,
                                     lidbox_stream_t stream);
+/* lidbox_mla_attention_bwd on B utterances of different lengths that lie end to end:
+ *   z, dz        [total_T][K]: utterance b owns the rows row_offsets[b] .. row_offsets[b + 1]
+ *   row_offsets  device int64 [B + 1], as in lidbox_mla_attention_ragged_fwd (trusted alike)
+ *   max_T        the longest utterance (the host knows it): it sizes the grid alone, (B, min(cdiv(max_T, rows per workgroup),
+ *                cdiv(2048, B))), the dense rule.  A workgroup whose first row lies behind its utterance's end leaves at once;
+ *                a max_T below the longest utterance costs trips of the row loop, never rows
+ *   att, datt    column slices, rows ld_att, ld_datt >= K floats apart
+ *   colsum       [B][K], as lidbox_mla_attention_ragged_fwd wrote it
+ * Both backward kernels run one __device__ function on an utterance's rows, and backward has no sum over t, so utterance b's
+ * rows of dz are bit for bit what lidbox_mla_attention_bwd gives at B = 1, T = T_b on z + row_offsets[b] K, dz + row_offsets[b] K
+ * and the utterance's att, colsum and datt rows, whatever the neighbours and the place in the batch.  The load path is chosen
+ * once: 16-byte loads / stores when K % 4 == 0 and z and dz are 16-byte aligned.  No atomics, no LDS, no communication
+ * between workgroups.  1 <= K <= 1024, 0 <= B < 2^31, max_T >= 1 when B > 0; B == 0 returns without a launch. */
+int lidbox_mla_attention_ragged_bwd(const float* z, const long* row_offsets, long B, int max_T, int K, const float* att, long ld_att,
+                                    const float* colsum, const float* datt, long ld_datt, float* dz, lidbox_stream_t stream);
 /* BatchNormalization apply -> ReLU -> Dropout(rate) on x viewed as [R][C] in one pass (DenseBlock, multilevel_attention.py:53-57):
  * y = relu(x * scale[c] + shift[c]) * mask, mask = 0 with probability `rate` and 1 / (1 - rate) otherwise, drawn from
  * (seed, *step_counter, r, c) exactly as lidbox_dropout_rows draws it (step_counter: device int64, NULL reads 0).

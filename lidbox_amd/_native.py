@@ -247,6 +247,7 @@ _SIGS = {
     "lidbox_mla_attention_fwd": (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp]),
     "lidbox_mla_attention_bwd": (_i, [_vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _vp, _vp]),
     "lidbox_mla_attention_ragged_fwd": (_i, [_vp, _vp, _l, _i, _vp, _l, _vp, _vp]),
+    "lidbox_mla_attention_ragged_bwd": (_i, [_vp, _vp, _l, _i, _i, _vp, _l, _vp, _vp, _l, _vp, _vp]),
     "lidbox_bn_relu_dropout_fwd": (_i, [_vp, _l, _i, _vp, _vp, _f, C.c_ulonglong, _vp, _vp, _vp]),
     "lidbox_bn_relu_dropout_bwd": (_i, [_vp, _l, _i, _vp, _vp, _f, C.c_ulonglong, _vp, _vp, _vp, _vp]),
     "lidbox_backend_score": (_i, [_vp, _l, _i, _l, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _l, _vp]),

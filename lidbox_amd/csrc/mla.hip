@@ -1,7 +1,7 @@
 // mla.hip -- kernels of the multi-level attention classifier (lidbox_amd.models.multilevel_attention, reference
 // lidbox/models/multilevel_attention.py:21-85; Yu et al. 2018):
-//   * the attention pooling of one level and its backward pass (lidbox_mla_attention_fwd / _bwd), and the forward pooling of
-//     utterances of different lengths that lie end to end (lidbox_mla_attention_ragged_fwd: the same per-utterance code);
+//   * the attention pooling of one level and its backward pass (lidbox_mla_attention_fwd / _bwd), and both on utterances of
+//     different lengths that lie end to end (lidbox_mla_attention_ragged_fwd / _bwd: the same per-utterance code);
 //   * BatchNormalization-apply + ReLU + Dropout over [R, C] activations in one pass, forward and backward
 //     (lidbox_bn_relu_dropout_fwd / _bwd), bit-identical to lidbox_bn_relu_* composed with lidbox_dropout_rows.
 //
@@ -193,16 +193,15 @@ __global__ __launch_bounds__(VEC * NJ >= 16 ? 512 : 1024) void mla_attention_rag
 }
 
 // dp = m g (v - att) / s,  dz = p (dp - sum_j dp_j p_j) + g (c / s) v (1 - v),  m = (lo <= p <= hi)
-// grid (B, rows split), block NW * 64
+// One utterance's share of a backward workgroup: zb [T, K] -> dzb [T, K] from the utterance's att, colsum and datt rows.  The
+// workgroup is blockIdx.y of gridDim.y over the rows.  The dense and the ragged backward kernel both call it, so a row's bits
+// are those of (its z, att, colsum, datt, K) in either: there is no sum over t.
 template <int VEC, int NJ>
-__global__ __launch_bounds__(512) void mla_attention_bwd_kernel(const float* __restrict__ z, const float* __restrict__ att, long ld_att,
-                                                                const float* __restrict__ colsum, const float* __restrict__ datt,
-                                                                long ld_datt, int T, int K, int G, float* __restrict__ dz) {
-    const int b = blockIdx.x;
+__device__ __forceinline__ void mla_attention_bwd_rows(const float* __restrict__ zb, int T, int K, int G, const float* __restrict__ att_b,
+                                                       const float* __restrict__ colsum_b, const float* __restrict__ datt_b,
+                                                       float* __restrict__ dzb) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, NW = blockDim.x >> 6;
     const int rpw = 64 / G, slot = lane / G, gl = lane - slot * G;
-    const float* zb = z + (long)b * T * K;
-    float* dzb = dz + (long)b * T * K;
     float zr[NJ][VEC], pr[NJ][VEC], gs[NJ][VEC], at[NJ][VEC];
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
@@ -210,8 +209,8 @@ __global__ __launch_bounds__(512) void mla_attention_bwd_kernel(const float* __r
         for (int e = 0; e < VEC; ++e) {
             const int col = (gl + G * j) * VEC + e;
             const bool ok = col < K;
-            gs[j][e] = ok ? datt[(long)b * ld_datt + col] / colsum[(long)b * K + col] : 0.f;
-            at[j][e] = ok ? att[(long)b * ld_att + col] : 0.f;
+            gs[j][e] = ok ? datt_b[col] / colsum_b[col] : 0.f;
+            at[j][e] = ok ? att_b[col] : 0.f;
         }
     const int step = (int)gridDim.y * NW * rpw;
     for (int t0 = ((int)blockIdx.y * NW + w) * rpw; t0 < T; t0 += step) {
@@ -251,6 +250,31 @@ __global__ __launch_bounds__(512) void mla_attention_bwd_kernel(const float* __r
             }
         }
     }
+}
+
+// grid (B, rows split), block NW * 64
+template <int VEC, int NJ>
+__global__ __launch_bounds__(512) void mla_attention_bwd_kernel(const float* __restrict__ z, const float* __restrict__ att, long ld_att,
+                                                                const float* __restrict__ colsum, const float* __restrict__ datt,
+                                                                long ld_datt, int T, int K, int G, float* __restrict__ dz) {
+    const int b = blockIdx.x;
+    mla_attention_bwd_rows<VEC, NJ>(z + (long)b * T * K, T, K, G, att + (long)b * ld_att, colsum + (long)b * K, datt + (long)b * ld_datt,
+                                    dz + (long)b * T * K);
+}
+
+// the same on utterances that lie end to end: z, dz [total_T, K], utterance b = rows row_offsets[b] .. row_offsets[b + 1].
+// grid (B, rows split of the longest utterance), block NW * 64; a workgroup whose first row lies behind its utterance's end
+// leaves at once
+template <int VEC, int NJ>
+__global__ __launch_bounds__(512) void mla_attention_ragged_bwd_kernel(const float* __restrict__ z, const long* __restrict__ row_offsets,
+                                                                       const float* __restrict__ att, long ld_att,
+                                                                       const float* __restrict__ colsum, const float* __restrict__ datt,
+                                                                       long ld_datt, int K, int G, float* __restrict__ dz) {
+    const int b = blockIdx.x;
+    const long r0 = row_offsets[b];
+    const int T = (int)(row_offsets[b + 1] - r0);
+    if ((int)blockIdx.y * (int)(blockDim.x >> 6) * (64 / G) >= T) return;
+    mla_attention_bwd_rows<VEC, NJ>(z + r0 * K, T, K, G, att + (long)b * ld_att, colsum + (long)b * K, datt + (long)b * ld_datt, dz + r0 * K);
 }
 
 // counter-based uniform in [0, 1) and the BatchNormalization expression: the SAME expressions as nnops.hip's hash_uniform
@@ -339,6 +363,18 @@ void launch_bwd(const MlaPlan& p, hipStream_t st, const float* z, const float* a
                        datt, ld_datt, T, K, p.G, dz);
 }
 
+template <int VEC, int NJ>
+void launch_ragged_bwd(const MlaPlan& p, hipStream_t st, const float* z, const long* row_offsets, long B, int max_T, const float* att,
+                       long ld_att, const float* colsum, const float* datt, long ld_datt, int K, float* dz) {
+    const int nw = 8;
+    const int rows_per_wg = nw * (64 / p.G);
+    long gy = lbx_cdiv(max_T, rows_per_wg);         // the dense rule on the longest utterance
+    const long want = lbx_cdiv(2048, B);
+    if (gy > want) gy = want;
+    hipLaunchKernelGGL((mla_attention_ragged_bwd_kernel<VEC, NJ>), dim3((unsigned)B, (unsigned)gy), dim3(nw * 64), 0, st, z, row_offsets, att,
+                       ld_att, colsum, datt, ld_datt, K, p.G, dz);
+}
+
 }  // namespace
 
 extern "C" int lidbox_mla_attention_fwd(const float* z, int B, int T, int K, float* att, long ld_att, float* colsum,
@@ -415,6 +451,34 @@ extern "C" int lidbox_mla_attention_bwd(const float* z, const float* att, long l
         else MLA_BWD(1, 16);
     }
 #undef MLA_BWD
+    LBX_LAUNCH_OK();
+    return LIDBOX_OK;
+}
+
+extern "C" int lidbox_mla_attention_ragged_bwd(const float* z, const long* row_offsets, long B, int max_T, int K, const float* att,
+                                               long ld_att, const float* colsum, const float* datt, long ld_datt, float* dz,
+                                               lidbox_stream_t stream) {
+    LBX_ARG(B >= 0 && B <= 0x7fffffffL && K >= 1, "0 <= B < 2^31, K >= 1");
+    LBX_ARG(K <= MLA_MAX_K, "K <= 1024");
+    LBX_ARG(B == 0 || max_T >= 1, "max_T >= 1");
+    LBX_ARG(z && row_offsets && att && colsum && datt && dz, "z, row_offsets, att, colsum, datt, dz != NULL");
+    LBX_ARG(ld_att >= K && ld_datt >= K, "ld_att, ld_datt >= K");
+    if (B == 0) return LIDBOX_OK;
+    const MlaPlan p = mla_plan(K, K % 4 == 0 && aligned16(z) && aligned16(dz));        // every utterance's first row is then aligned
+    hipStream_t st = (hipStream_t)stream;
+#define MLA_RBWD(V, N) launch_ragged_bwd<V, N>(p, st, z, row_offsets, B, max_T, att, ld_att, colsum, datt, ld_datt, K, dz)
+    if (p.vec == 4) {
+        if (p.nj == 1) MLA_RBWD(4, 1);
+        else if (p.nj == 2) MLA_RBWD(4, 2);
+        else MLA_RBWD(4, 4);
+    } else {
+        if (p.nj == 1) MLA_RBWD(1, 1);
+        else if (p.nj == 2) MLA_RBWD(1, 2);
+        else if (p.nj == 4) MLA_RBWD(1, 4);
+        else if (p.nj == 8) MLA_RBWD(1, 8);
+        else MLA_RBWD(1, 16);
+    }
+#undef MLA_RBWD
     LBX_LAUNCH_OK();
     return LIDBOX_OK;
 }

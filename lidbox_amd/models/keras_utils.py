@@ -371,6 +371,20 @@ class KerasWrapper:
         buf[1].copy_(y)
         return buf
 
+    @staticmethod
+    def _is_ragged(x):
+        """a dataset element whose inputs are a pair (X [total_T, D], row_offsets [B + 1]): utterances of different lengths,
+        laid end to end"""
+        return isinstance(x, (tuple, list)) and len(x) == 2 and np.ndim(x[1]) == 1 and np.ndim(x[0]) == 2
+
+    def _stage_ragged(self, x, y):
+        """(X on the device, offsets as a host int64 array, labels on the device) of a ragged element; the step is eager, so
+        nothing has to keep its address"""
+        dev = self.keras_model.device
+        X = torch.as_tensor(x[0], dtype=torch.float32).to(dev).contiguous()
+        ro = np.asarray(x[1].cpu() if torch.is_tensor(x[1]) else x[1], np.int64).reshape(-1)
+        return X, ro, torch.as_tensor(y).to(torch.int32).reshape(-1).to(dev)
+
     def _eval_loss(self, out, y):
         """(mean loss of the batch, the scores the metrics read) on the library's own kernels: tf.math.l2_normalize + the loss for
         SparseAngularProximity (reference losses.py:25-52), sparse categorical cross-entropy on the model's log-probabilities /
@@ -396,16 +410,21 @@ class KerasWrapper:
         return float(loss), out
 
     def evaluate(self, dataset):
-        """mean loss and metric values over a dataset of (inputs, targets) batches (Keras `Model.evaluate`)"""
+        """mean loss and metric values over a dataset of (inputs, targets) batches (Keras `Model.evaluate`); inputs that are a
+        pair (X, row_offsets) go through the model's predict_ragged"""
         for m in self.metrics:
             m.reset_states()
         total, count = 0.0, 0
         for x, y in dataset:
-            xs, ys = self._stage(x, y)
-            out = self.keras_model(xs, training=False)
+            if self._is_ragged(x):
+                X, ro, ys = self._stage_ragged(x, y)
+                out, bs = self.keras_model.predict_ragged(X, ro), len(ro) - 1
+            else:
+                xs, ys = self._stage(x, y)
+                out, bs = self.keras_model(xs, training=False), xs.shape[0]
             loss, scores = self._eval_loss(out, ys)
-            total += loss * xs.shape[0]
-            count += xs.shape[0]
+            total += loss * bs
+            count += bs
             for m in self.metrics:
                 if isinstance(m, lidbox_metrics.AverageDetectionCost):
                     m._update_sparse(ys, scores)
@@ -419,7 +438,8 @@ class KerasWrapper:
         return logs
 
     def fit(self, training_dataset, validation_dataset, user_kwargs):
-        """reference keras_utils.py:190-203.  Datasets are re-iterable collections of (inputs, targets) batches;
+        """reference keras_utils.py:190-203.  Datasets are re-iterable collections of (inputs, targets) batches; inputs that
+        are a pair (X [total_T, D], row_offsets [B + 1]) are utterances of different lengths and take Trainer.train_step_ragged;
         user_kwargs: epochs, steps_per_epoch, validation_freq, verbose.  Returns {"history": {...}, "epoch": [...]}"""
         kwargs = {"shuffle": False, "validation_freq": 1, "verbose": 2}
         kwargs.update(user_kwargs)
@@ -436,6 +456,11 @@ class KerasWrapper:
             for step, (x, y) in enumerate(training_dataset):
                 if steps_per_epoch is not None and step >= int(steps_per_epoch):
                     break
+                if self._is_ragged(x):
+                    X, ro, ys = self._stage_ragged(x, y)
+                    losses.append((self.trainer.train_step_ragged(X, ro, ys).clone(), len(ro) - 1))
+                    n += len(ro) - 1
+                    continue
                 xs, ys = self._stage(x, y)
                 # data parallelism: the global batch of this step, exchanged on every rank at every step (rank-symmetric; the
                 # shards of a last, smaller batch need not shrink together)

@@ -26,6 +26,11 @@ Parameters carry the Keras names of the inner layers (`dense_block1_fc.W`, `dens
 `outputs.W`).
 
 Ragged pass (inference): `ragged_pass.RaggedPass` with `_ragged_pass`, which needs no layout of its own.
+
+Ragged training pass: `forward_ragged_train` / `backward_ragged` on a `RaggedTrainWorkspace`.  They are the launches of
+`forward_ws(training=True)` / `backward_head_ws` (one body each, `_forward_levels` / `_backward_levels`) over the R = total_T
+concatenated frames, with the two pooling calls swapped for lidbox_mla_attention_ragged_fwd (with colsum) / _ragged_bwd.  The
+batch statistics are those of the real frames and a mask's row is the row in the concatenation.
 """
 import ctypes
 
@@ -34,7 +39,7 @@ import torch
 from .. import _native as nv
 from .flat import FlatModel, Workspace, _rows
 from .gru_rnn import BatchNormSpec
-from .ragged_pass import EmbeddingExtractor, RaggedPass, upload_int64
+from .ragged_pass import EmbeddingExtractor, RaggedPass, RaggedWorkspace, upload_int64
 from .tdnn import DenseSpec
 
 MAX_OUTPUTS = 1024          # lidbox_mla_attention_*: a row of class logits lives in the registers of one wave
@@ -46,7 +51,6 @@ class _Workspace(Workspace):
     def __init__(self, model, B, T):
         dev = model.device
         f32 = dict(dtype=torch.float32, device=dev)
-        lib = nv.lib
         self.B, self.T = B, T
         H, K, L, D = model.units, model.output_dim, model.levels, model.input_dim
         R = B * T
@@ -65,19 +69,64 @@ class _Workspace(Workspace):
         self.dh = [torch.zeros((B, K), **f32)]
         self.logp = torch.zeros((B, K), **f32)
         self.loss = torch.zeros(4, **f32)
-        gws, tws = 0, 16
-        cin = D
-        for _ in range(L):
-            gws = max(gws, lib.lidbox_gemm_rows_workspace(R, H, cin), lib.lidbox_gemm_rows_workspace(R, cin, H),
-                      lib.lidbox_gemm_rows_workspace(R, K, H), lib.lidbox_gemm_rows_workspace(R, H, K))
-            tws = max(tws, lib.lidbox_gemm_tn_workspace(R, cin, H), lib.lidbox_gemm_tn_workspace(R, H, K))
-            cin = H
-        gws = max(gws, lib.lidbox_gemm_rows_workspace(B, K, L * K), lib.lidbox_gemm_rows_workspace(B, L * K, K))
-        tws = max(tws, lib.lidbox_gemm_tn_workspace(B, L * K, K))
-        self.gemm_ws = torch.empty(max(16, gws), dtype=torch.uint8, device=dev)
+        gws, tws, bws = model.train_byte_needs(R, B)
+        self.gemm_ws = torch.empty(gws, dtype=torch.uint8, device=dev)
         self.tn_ws = torch.empty(tws, dtype=torch.uint8, device=dev)
-        self.bn_ws = torch.empty(max(16, lib.lidbox_bn_workspace(max(R, 1), H)), dtype=torch.uint8, device=dev)
+        self.bn_ws = torch.empty(bws, dtype=torch.uint8, device=dev)
         self.pending = []
+
+    def pool_fwd(self, model, l, st):
+        K, L = model.output_dim, model.levels
+        nv.check(nv.lib.lidbox_mla_attention_fwd(nv.ptr(self.z[l]), self.B, self.T, K, ctypes.c_void_p(self.att.data_ptr() + 4 * l * K),
+                                                 L * K, nv.ptr(self.colsum[l]), st))
+
+    def pool_bwd(self, model, l, st):
+        K, L = model.output_dim, model.levels
+        nv.check(nv.lib.lidbox_mla_attention_bwd(nv.ptr(self.z[l]), ctypes.c_void_p(self.att.data_ptr() + 4 * l * K), L * K,
+                                                 nv.ptr(self.colsum[l]), ctypes.c_void_p(self.datt.data_ptr() + 4 * l * K), L * K,
+                                                 self.B, self.T, K, nv.ptr(self.dz), st))
+
+
+class RaggedTrainWorkspace(RaggedWorkspace):
+    """Device buffers of the ragged training pass, sized by the capacities `cap_rows` and `cap_B` (growth:
+    `RaggedWorkspace.reserve`); a pass uses the front of them.  Unlike the inference workspace it keeps every level's `a`, `y` and
+    `z` for backward.  `x` is the caller's X [R, D] itself, `ro_table` the pass's one upload.  The byte workspaces are reserved per
+    call for the call's own R and B (`reserve_bytes`)."""
+
+    buffers_prefix = "_ragged_train_buffers_"
+
+    def __init__(self, model):
+        super().__init__(model)
+        self.tn_ws = torch.empty(16, dtype=torch.uint8, device=model.device)
+        self.bn_ws = torch.empty(16, dtype=torch.uint8, device=model.device)
+        self.x = self.ro_table = self.ro_dev = None
+        self.R = self.max_T = 0
+        self.grown = 0                     # how often a capacity was exceeded
+        self.pending = []
+
+    def reserve(self, model, **needs):
+        caps = (self.cap_rows, self.cap_B)
+        super().reserve(model, **needs)
+        if (self.cap_rows, self.cap_B) != caps:
+            self.grown += 1
+            for name in ("ap_zn", "ap_dzn", "ap_per", "ap_scores"):          # the Trainer's angular-proximity buffers, sized by cap_B
+                self.__dict__.pop(name, None)
+
+    def reserve_bytes(self, model, R, B):
+        for name, n in zip(("gemm_ws", "tn_ws", "bn_ws"), model.train_byte_needs(R, B)):
+            if n > getattr(self, name).numel():
+                setattr(self, name, torch.empty(int(n), dtype=torch.uint8, device=model.device))
+
+    def pool_fwd(self, model, l, st):
+        K, L = model.output_dim, model.levels
+        nv.check(nv.lib.lidbox_mla_attention_ragged_fwd(nv.ptr(self.z[l]), self.ro_dev, self.B, K,
+                                                        ctypes.c_void_p(self.att.data_ptr() + 4 * l * K), L * K, nv.ptr(self.colsum[l]), st))
+
+    def pool_bwd(self, model, l, st):
+        K, L = model.output_dim, model.levels
+        nv.check(nv.lib.lidbox_mla_attention_ragged_bwd(nv.ptr(self.z[l]), self.ro_dev, self.B, self.max_T, K,
+                                                        ctypes.c_void_p(self.att.data_ptr() + 4 * l * K), L * K, nv.ptr(self.colsum[l]),
+                                                        ctypes.c_void_p(self.datt.data_ptr() + 4 * l * K), L * K, nv.ptr(self.dz), st))
 
 
 class MultilevelAttentionModel(FlatModel, RaggedPass):
@@ -115,9 +164,23 @@ class MultilevelAttentionModel(FlatModel, RaggedPass):
         self.add_param("outputs.b", (K,))
         self._finish(seed)
 
-    def _in_rows(self, ws, l):
-        """(rows descriptor, width) of level l's input: the model input, or the previous level's output"""
-        R = ws.B * ws.T
+    def train_byte_needs(self, R, B):
+        """bytes of (gemm_ws, tn_ws, bn_ws) a training pass over R frames of B utterances needs"""
+        lib = nv.lib
+        H, K, L = self.units, self.output_dim, self.levels
+        gws, tws = 0, 16
+        cin = self.input_dim
+        for _ in range(L):
+            gws = max(gws, lib.lidbox_gemm_rows_workspace(R, H, cin), lib.lidbox_gemm_rows_workspace(R, cin, H),
+                      lib.lidbox_gemm_rows_workspace(R, K, H), lib.lidbox_gemm_rows_workspace(R, H, K))
+            tws = max(tws, lib.lidbox_gemm_tn_workspace(R, cin, H), lib.lidbox_gemm_tn_workspace(R, H, K))
+            cin = H
+        gws = max(gws, lib.lidbox_gemm_rows_workspace(B, K, L * K), lib.lidbox_gemm_rows_workspace(B, L * K, K))
+        tws = max(tws, lib.lidbox_gemm_tn_workspace(B, L * K, K))
+        return max(16, gws), tws, max(16, lib.lidbox_bn_workspace(max(R, 1), H))
+
+    def _in_rows(self, ws, l, R):
+        """(rows descriptor, width) of level l's input over R rows: the model input, or the previous level's output"""
         if l == 0:
             return _rows(ws.x.data_ptr(), 0, self.input_dim, 1, R), self.input_dim
         return _rows(ws.y[l - 1].data_ptr(), 0, self.units, 1, R), self.units
@@ -140,18 +203,22 @@ class MultilevelAttentionModel(FlatModel, RaggedPass):
         BatchNormalization layers (update_moving=False leaves the running statistics untouched) and switches the Dropout
         on.  Returns the log-probs / probabilities / logits (output_activation None); stop_before_output: the concatenated
         attention outputs [B, L*K]."""
+        return self._forward_levels(ws, ws.B * ws.T, training, update_moving, stop_before_output)
+
+    def _forward_levels(self, ws, R, training, update_moving, stop_before_output=False):
+        """the forward launches over the R rows of ws.B utterances, dense ([B, T, D] in ws.x, R = B T) or ragged (ws.x the
+        concatenated frames): they differ in where the rows come from and in `ws.pool_fwd`"""
         st = nv.current_stream()
         lib = nv.lib
-        B, T = ws.B, ws.T
+        B = ws.B
         H, K, L = self.units, self.output_dim, self.levels
-        R = B * T
         gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
         if B == 0:
             return ws.att if stop_before_output else ws.logp
         rate = self.dropout_rate if training else 0.0
         for l in range(L):
             fc, bn, at = self.blocks[l] + "_fc", self.bns[l], self.attentions[l]
-            X, cin = self._in_rows(ws, l)
+            X, cin = self._in_rows(ws, l, R)
             nv.check(lib.lidbox_gemm_nn(X, self._p(fc + ".W"), H, _rows(ws.a[l].data_ptr(), 0, H, 1, R), cin, H, nv.EPI_BIAS,
                                         self._p(fc + ".b"), gws, gws_n, st))
             cp = self._bn_fwd(bn, ws.a[l], R, H, ws.consts[l], None, ws, training, update_moving)
@@ -159,8 +226,7 @@ class MultilevelAttentionModel(FlatModel, RaggedPass):
                                                     self._dropout_step_ptr(), nv.ptr(ws.y[l]), st))
             nv.check(lib.lidbox_gemm_nn(_rows(ws.y[l].data_ptr(), 0, H, 1, R), self._p(at + ".W"), K,
                                         _rows(ws.z[l].data_ptr(), 0, K, 1, R), H, K, nv.EPI_BIAS, self._p(at + ".b"), gws, gws_n, st))
-            nv.check(lib.lidbox_mla_attention_fwd(nv.ptr(ws.z[l]), B, T, K, ctypes.c_void_p(ws.att.data_ptr() + 4 * l * K), L * K,
-                                                  nv.ptr(ws.colsum[l]), st))
+            ws.pool_fwd(self, l, st)
         if stop_before_output:
             return ws.att
         nv.check(lib.lidbox_gemm_nn(_rows(ws.att.data_ptr(), 0, L * K, 1, B), self._p("outputs.W"), K,
@@ -237,11 +303,14 @@ class MultilevelAttentionModel(FlatModel, RaggedPass):
     def backward_head_ws(self, ws):
         """the whole backward pass of a training-mode forward (dh[-1] holds d loss / d logits): the output layer, then the
         levels from the top down.  Fills flat_grad (overwrites)."""
+        self._backward_levels(ws, ws.B * ws.T)
+
+    def _backward_levels(self, ws, R):
+        """the backward launches over the R rows of ws.B utterances, dense or ragged (`_forward_levels`): `ws.pool_bwd`"""
         st = nv.current_stream()
         lib = nv.lib
-        B, T = ws.B, ws.T
+        B = ws.B
         H, K, L = self.units, self.output_dim, self.levels
-        R = B * T
         ws.pending = []
         gws, gws_n = nv.ptr(ws.gemm_ws), ws.gemm_ws.numel()
         tws, tws_n = nv.ptr(ws.tn_ws), ws.tn_ws.numel()
@@ -260,9 +329,7 @@ class MultilevelAttentionModel(FlatModel, RaggedPass):
             fc, bn, at = self.blocks[l] + "_fc", self.bns[l], self.attentions[l]
             yl = _rows(ws.y[l].data_ptr(), 0, H, 1, R)
             # attention{l}: dz from the level's slices of att / datt, then its Dense
-            nv.check(lib.lidbox_mla_attention_bwd(nv.ptr(ws.z[l]), ctypes.c_void_p(ws.att.data_ptr() + 4 * l * K), L * K,
-                                                  nv.ptr(ws.colsum[l]), ctypes.c_void_p(ws.datt.data_ptr() + 4 * l * K), L * K,
-                                                  B, T, K, nv.ptr(ws.dz), st))
+            ws.pool_bwd(self, l, st)
             nv.check(lib.lidbox_gemm_tn(yl, dz, self._p(at + ".W", True), K, H, K, 0, self._p(at + ".b", True), tws, tws_n, st))
             # gradient of y_l: the attention branch, on top of the next level's da W_fc^T below the top level
             nv.check(lib.lidbox_gemm_nt(dz, self._p(at + ".W"), K, dy, K, H, nv.EPI_NONE if l == L - 1 else nv.EPI_ACCUM, None,
@@ -275,10 +342,49 @@ class MultilevelAttentionModel(FlatModel, RaggedPass):
                                                     nv.ptr(ws.dy), st))
             self._bn_bwd(bn, ws.a[l], R, H, c, ws.dy, 0, ws.da, ws)
             # dense_block{l}_fc
-            X, cin = self._in_rows(ws, l)
+            X, cin = self._in_rows(ws, l, R)
             nv.check(lib.lidbox_gemm_tn(X, da, self._p(fc + ".W", True), H, cin, H, 0, self._p(fc + ".b", True), tws, tws_n, st))
             if l > 0:
                 nv.check(lib.lidbox_gemm_nt(da, self._p(fc + ".W"), H, dy, H, cin, nv.EPI_NONE, None, gws, gws_n, st))
+
+    # ------------------------------------------------------------------ ragged training pass
+    def _ragged_train_buffers_rows(self, cap):
+        """per frame; every level's a, y and z are kept for backward"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        H, K, L = self.units, self.output_dim, self.levels
+        return dict(a=[torch.zeros((cap, H), **f32) for _ in range(L)], y=[torch.zeros((cap, H), **f32) for _ in range(L)],
+                    z=[torch.zeros((cap, K), **f32) for _ in range(L)], consts=[torch.zeros((4, H), **f32) for _ in range(L)],
+                    dz=torch.zeros((cap, K), **f32), dy=torch.zeros((cap, H), **f32), da=torch.zeros((cap, H), **f32))
+
+    def _ragged_train_buffers_B(self, cap):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        K, L = self.output_dim, self.levels
+        return dict(colsum=[torch.zeros((cap, K), **f32) for _ in range(L)], att=torch.zeros((cap, L * K), **f32),
+                    datt=torch.zeros((cap, L * K), **f32), h=[torch.zeros((cap, K), **f32)], dh=[torch.zeros((cap, K), **f32)],
+                    logp=torch.zeros((cap, K), **f32), loss=torch.zeros(4, **f32))
+
+    def ragged_train_workspace(self, rows, B):
+        """the model's one RaggedTrainWorkspace, with room for `rows` frames of `B` utterances"""
+        ws = getattr(self, "_rtws", None)
+        if ws is None:
+            ws = self._rtws = RaggedTrainWorkspace(self)
+        ws.reserve(self, rows=rows, B=B)
+        ws.reserve_bytes(self, rows, B)
+        return ws
+
+    def forward_ragged_train(self, ws, X, ro, update_moving=True):
+        """training-mode forward on X [total_T, D] (float32, contiguous, on the device: the GEMM operand as it stands, which
+        must stay alive until backward_ragged has run) with the offsets ro (host int64 [B + 1], already checked by
+        ragged_pass.ragged_input; no empty utterance).  ws: ragged_train_workspace(total_T, B).  Returns the model output, B
+        rows at the front of a workspace buffer."""
+        ws.B, ws.R, ws.x = len(ro) - 1, int(X.shape[0]), X
+        ws.max_T = int((ro[1:] - ro[:-1]).max()) if ws.B else 0
+        ws.ro_table, (ws.ro_dev,) = upload_int64([ro], self.device)
+        return self._forward_levels(ws, ws.R, True, update_moving)[:ws.B]
+
+    def backward_ragged(self, ws):
+        """the backward pass of forward_ragged_train (dh[-1][:B] holds d loss / d logits).  Fills flat_grad (overwrites)."""
+        self._backward_levels(ws, ws.R)
 
 
 def create(input_shape, num_outputs, output_activation="log_softmax", L=2, H=512, seed=None, device=None,
@@ -300,4 +406,4 @@ def as_embedding_extractor(model):
     return EmbeddingExtractor(model)
 
 
-__all__ = ["MultilevelAttentionModel", "EmbeddingExtractor", "as_embedding_extractor", "create", "loader"]
+__all__ = ["MultilevelAttentionModel", "RaggedTrainWorkspace", "EmbeddingExtractor", "as_embedding_extractor", "create", "loader"]

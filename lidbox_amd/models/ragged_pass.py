@@ -56,7 +56,9 @@ class RaggedWorkspace:
     """Device buffers of a model's ragged pass, sized by named capacities (`cap_rows` rows and `cap_B` utterances in every
     model; crnn's `cap_rec`, clstm's `cap_frames`); a pass that needs less of a capacity uses the front of its buffers.  The
     buffers of capacity <name> come from the model's `_ragged_buffers_<name>(cap)` as a dict, whose entries become
-    attributes."""
+    attributes (`buffers_prefix`: a subclass with buffers of its own names another family of such methods)."""
+
+    buffers_prefix = "_ragged_buffers_"
 
     def __init__(self, model):
         self.cap_rows = self.cap_B = self.B = 0
@@ -69,7 +71,7 @@ class RaggedWorkspace:
             if n > cap:
                 cap = max(int(n), cap + cap // 2)
                 setattr(self, "cap_" + name, cap)
-                self.__dict__.update(getattr(model, "_ragged_buffers_" + name)(cap))
+                self.__dict__.update(getattr(model, self.buffers_prefix + name)(cap))
 
     def reserve_gemm_ws(self, model, nbytes):
         if nbytes > self.gemm_ws.numel():

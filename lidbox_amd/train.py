@@ -354,6 +354,15 @@ class Trainer:
             out = ws.logp
         else:
             out = model.forward_ws(ws, training=True, update_moving=not self._warming)
+        self._loss_head(ws, out, labels, B, scale)
+        if nxt is not None:
+            torch.cuda.current_stream().wait_stream(self._prefetch_stream)      # the prefetch joins behind the forward pass
+
+    def _loss_head(self, ws, out, labels, B, scale):
+        """the loss part of a step, dense or ragged: loss (ws.loss) and d loss / d logits (ws.dh[-1]) from the model output
+        `out` [B, N] of the forward pass that has just run on ws, scaled by `scale` = d(mean loss)/d(per-example loss), and the
+        update of the streaming metric.  B rows at the front of the workspace's buffers."""
+        lib, st = nv.lib, nv.current_stream()
         if self.loss_kind == "nll":
             if not getattr(ws, "output_layer_done", False):
                 nv.check(lib.lidbox_nll_fwd_bwd(nv.ptr(out), nv.ptr(labels), B, out.shape[1], scale,
@@ -365,25 +374,24 @@ class Trainer:
         else:
             D = out.shape[1]
             zn, dzn, per = self._ap_buffers(ws, D)
+            scores = ws.ap_scores[:B]
             want_scores = self.metric is not None and not self._warming
             if D <= 4096:
                 # normalise -> loss + gradient -> gradient through the normalisation -> predict() scores: one launch
                 nv.check(lib.lidbox_ap_head_fwd_bwd(nv.ptr(out), nv.ptr(labels), B, D, self.ap.N, self.ap.delta_weight, scale, None,
-                                                    nv.ptr(per), nv.ptr(ws.dh[-1]), nv.ptr(ws.ap_scores) if want_scores else None, st))
+                                                    nv.ptr(per), nv.ptr(ws.dh[-1]), nv.ptr(scores) if want_scores else None, st))
             else:
                 nv.check(lib.lidbox_l2_normalize_fwd(nv.ptr(out), B, D, nv.ptr(zn), st))
                 nv.check(lib.lidbox_ap_loss_fwd_bwd(nv.ptr(zn), nv.ptr(labels), B, D, self.ap.N, self.ap.delta_weight,
                                                     scale, nv.ptr(per), nv.ptr(dzn), st))
                 nv.check(lib.lidbox_l2_normalize_bwd(nv.ptr(out), nv.ptr(dzn), B, D, nv.ptr(ws.dh[-1]), st))
                 if want_scores:
-                    nv.check(lib.lidbox_neg_acos(nv.ptr(zn), B, D, self.ap.N, nv.ptr(ws.ap_scores), st))
+                    nv.check(lib.lidbox_neg_acos(nv.ptr(zn), B, D, self.ap.N, nv.ptr(scores), st))
             nv.check(lib.lidbox_mean(nv.ptr(per), B, nv.ptr(ws.loss), st))
             if want_scores:
-                self.metric._update_sparse(labels, ws.ap_scores)
+                self.metric._update_sparse(labels, scores)
         if self.loss_kind in ("nll", "nll_probs") and self.metric is not None and not self._warming:
             self.metric._update_sparse(labels, out)
-        if nxt is not None:
-            torch.cuda.current_stream().wait_stream(self._prefetch_stream)      # the prefetch joins behind the forward pass
 
     def _extract_features(self, ws, signals, st):
         """waveforms -> the model's input buffer (ws.act[0] as currently selected): fused log-mel / MFCC kernel, CMVN in place"""
@@ -464,21 +472,23 @@ class Trainer:
 
     def _ap_buffers(self, ws, D):
         if not hasattr(ws, "ap_zn"):
-            ws.ap_zn = torch.zeros((ws.B, D), dtype=torch.float32, device=self.device)
+            cap = getattr(ws, "cap_B", ws.B)           # a ragged training workspace holds up to cap_B utterances
+            ws.ap_zn = torch.zeros((cap, D), dtype=torch.float32, device=self.device)
             ws.ap_dzn = torch.zeros_like(ws.ap_zn)
-            ws.ap_per = torch.zeros(ws.B, dtype=torch.float32, device=self.device)
-            ws.ap_scores = torch.zeros((ws.B, self.ap.N), dtype=torch.float32, device=self.device)
+            ws.ap_per = torch.zeros(cap, dtype=torch.float32, device=self.device)
+            ws.ap_scores = torch.zeros((cap, self.ap.N), dtype=torch.float32, device=self.device)
         return ws.ap_zn, ws.ap_dzn, ws.ap_per
 
-    def _backward_stage(self, ws, k):
+    def _backward_stage(self, ws, k, head=None):
         """Stage k of backward (k = 0 first).  Stage 0: dense head + pooling + the conv layers down to the highest
         split; stage j: the conv layers between two splits; the last stage ends at conv 0.  After stage k the
-        gradient bucket (num_buckets - 1 - k) is complete on the current stream."""
+        gradient bucket (num_buckets - 1 - k) is complete on the current stream.  head: what stage 0 runs in place of the
+        model's backward_head_ws (the ragged step: backward_ragged)."""
         convs = self.model.convs
         hi_edges = [len(convs)] + self.splits[::-1]              # exclusive upper conv index of every stage
         lo_edges = self.splits[::-1] + [0]
         if k == 0:
-            self.model.backward_head_ws(ws)
+            (head or self.model.backward_head_ws)(ws)
             if self.regularized:
                 self._apply_regularizers(ws)
         for i in range(hi_edges[k] - 1, lo_edges[k] - 1, -1):
@@ -747,6 +757,70 @@ class Trainer:
             finally:
                 self._warming = was
             self.model.backward_ws(ws)
+            if self.regularized:
+                self._apply_regularizers(ws)
+            return ws.loss[0], self.model.flat_grad
+
+    # ---------------------------------------------------------------- variable-length utterances
+    def _ragged_args(self, X, row_offsets, labels):
+        """the checks of a ragged step (ValueError on the host, before any launch); returns (X, offsets int64 [B + 1], labels)"""
+        from .models.ragged_pass import ragged_input
+        model = self.model
+        if not hasattr(model, "forward_ragged_train"):
+            raise ValueError("model %r (%s) has no ragged training pass" % (model.name, type(model).__name__))
+        if self.sync.active:
+            raise ValueError("a ragged train step under an active gradient exchange is not supported (one process only)")
+        if self.feature is not None:
+            raise ValueError("a ragged train step takes features [total_T, D]; this Trainer has a feature= front-end (waveform input)")
+        X, ro, lengths = ragged_input(X, row_offsets, model.model_input_dim)
+        B = len(lengths)
+        if B == 0:
+            raise ValueError("a ragged train step needs at least one utterance")
+        labels = nv.require_gpu_tensor(labels, "labels", torch.int32)
+        if labels.dim() != 1 or labels.shape[0] != B:
+            raise ValueError("labels must be [%d], one per utterance of row_offsets, got %s" % (B, tuple(labels.shape)))
+        return X, ro, labels
+
+    def _ragged_forward_loss(self, X, ro, labels):
+        """forward and loss of B utterances of different lengths in one pass; returns the model's RaggedTrainWorkspace"""
+        model, B = self.model, len(ro) - 1
+        model.dropout_step = self.adam_state
+        model.dropout_seed_mix = self._rank_mix()
+        ws = model.ragged_train_workspace(int(ro[-1]), B)
+        out = model.forward_ragged_train(ws, X, ro, update_moving=not self._warming)
+        self._loss_head(ws, out, labels, B, self._loss_scale(B))
+        return ws
+
+    def train_step_ragged(self, X, row_offsets, labels):
+        """One optimisation step on B utterances of different lengths, laid end to end: X [total_T, D] float32, contiguous, on
+        the device (it must stay unchanged until the step has run); row_offsets: host array [B + 1] (the conventions of
+        models/ragged_pass.py); labels int32 [B].  The BatchNormalization batch statistics are those of the real frames.  The
+        step runs eagerly: every GEMM's M is the call's own total_T.  Optimizer, learning-rate schedule and the step counter
+        as the dropout key are train_step's.  Returns the device scalar holding the mean loss."""
+        X, ro, labels = self._ragged_args(X, row_offsets, labels)
+        with torch.cuda.device(self.device):
+            self._step_global_batch = None
+            self._set_lr()
+            ws = self._ragged_forward_loss(X, ro, labels)
+            self._backward_stage(ws, 0, head=self.model.backward_ragged)
+            self._adam()
+            self._lr_advance()
+            return ws.loss[0]
+
+    def loss_and_grads_ragged(self, X, row_offsets, labels):
+        """forward + backward of train_step_ragged only (no optimizer; running statistics and streaming metrics stay put):
+        returns (loss, flat_grad view)."""
+        X, ro, labels = self._ragged_args(X, row_offsets, labels)
+        with torch.cuda.device(self.device):
+            self._step_global_batch = None
+            was = self._warming
+            self._warming = True
+            try:
+                ws = self._ragged_forward_loss(X, ro, labels)
+            finally:
+                self._warming = was
+            self.model.backward_ragged(ws)
+            self.model.flush_reduce_jobs(ws)
             if self.regularized:
                 self._apply_regularizers(ws)
             return ws.loss[0], self.model.flat_grad
